@@ -21,13 +21,22 @@ synchronize; the max over ranks is reported and value = total atoms / that
 time.  The rank graph is uploaded once (a step moves no host data, like the
 single-device step).
 
-Before timing, a full-size property check runs at the same size (a displaced
-8-atom cell tiled to the box: E = k^3 E_cell, per-image forces equal; through
-the halo exchanges when N > 1) and the run fails if it does not hold.
+A plain run does only what the headline figure needs: set-up, warm-up, the
+timed steps and the result line.  ``--dump-outputs DIR`` then writes what the
+last timed step returned (energy, atomic_energy, forces, virial) as
+``DIR/<name>.npy``; the inputs are seeded, so two builds can be compared
+output for output.
 
-Also reported: ``roofline`` for the dominant kernel class (HIP-event timed
-inside the library, on the stream the kernels run on) and ``cpu_baseline``
-(the oracle CPU restatement timed on this host on a bounded sample).
+``--full`` adds everything else, each leg outside the timed region:
+before timing, a full-size property check at the same size (a displaced
+8-atom cell tiled to the box: E = k^3 E_cell, per-image forces equal; through
+the halo exchanges when N > 1; the run fails if it does not hold); after it,
+``roofline`` and ``kernels`` for the dominant kernel class (HIP-event timed
+inside the library, on the stream the kernels run on), ``neighbor_list`` (the
+device graph build), ``cpu_baseline`` (the oracle CPU restatement timed on this
+host on a bounded sample), ``fine_tune`` (bench_train's step) and, N > 1,
+``distributed`` (the halo exchange against the compute).  Without ``--full``
+those fields of the line are null.
 """
 import argparse
 import json
@@ -61,6 +70,14 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs beside the headline figure: full-size property check, '
+                         'per-kernel stats pass and roofline, device neighbour list, cpu_baseline, '
+                         'fine_tune, and (N > 1) the distributed report; the --no-* options and '
+                         '--profile-only switch single legs of it off')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last one returned as '
+                         'DIR/<name>.npy (N > 1: DIR/<name>.rank<r>.npy per rank)')
     ap.add_argument('--cells', type=int, default=None,
                     help='n for an n^3 conventional-cell box: per rank (weak scaling, default '
                          '23) or in total (--strong, default 46)')
@@ -418,6 +435,30 @@ def distributed_report(drv, rg, world, step_ms, device):
     return info
 
 
+DUMP_BYTES = 64 * 1000 * 1000   # cap of one --dump-outputs directory (all ranks together)
+
+
+def dump_outputs(out, path, rank=0, world=1):
+    """--dump-outputs: the arrays the timed path returned in its last step
+    (the dict of model.energy_forces / ParallelE3GNN.evaluate) as
+    path/<name>.npy, float32 as computed (anything else, e.g. the owned-atom
+    indices of a rank, as float64); N > 1: path/<name>.rank<r>.npy per rank.
+    Should the arrays exceed the cap, every one keeps the same fixed share of
+    its rows (default_rng(0) sample, sorted), the same rows in every run."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for k, v in out.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        arrays[k] = np.asarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    budget = DUMP_BYTES // world
+    total = sum(a.nbytes for a in arrays.values())
+    for k, a in arrays.items():
+        if total > budget and a.ndim >= 1 and len(a) > 1:
+            keep = max(1, int(len(a) * budget / total))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(path, f'{k}.npy' if world == 1 else f'{k}.rank{rank}.npy'), a)
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -626,7 +667,7 @@ def main():
         log(f'box: {n} atoms, {E} edges; workspace after first step follows')
         if degrees:
             log(f'degrees: {degrees}')
-        if not args.no_parity_check:
+        if args.full and not args.no_parity_check:
             parity = parity_check_tiled(model, box, device) if args.system == 'hfo2' else \
                 parity_check_serial(model, cells, device, si)
             log(f'parity check: {parity}')
@@ -643,7 +684,7 @@ def main():
         pos, cell = si_diamond(total, sigma=0.05)
         n = len(pos)
         rg = build_rank_graph(pos, cell, np.full(n, si), 5.0, grid, rank)
-        if not args.no_parity_check:
+        if args.full and not args.no_parity_check:
             parity = parity_check_parallel(model, total, grid, rank, device, si)
             log(f'parity check: {parity}')
         drv = ParallelE3GNN(HipSegmentEngine(model))
@@ -682,9 +723,14 @@ def main():
     value = n * args.steps / dt  # whole system (world == 1: the one box)
     log(f'timed: {ms:.3f} ms/step')
     energy = float(out['energy'])
+    if args.dump_outputs:
+        dump_outputs(out, args.dump_outputs, rank, world)
+        log(f'outputs of the last timed step written to {args.dump_outputs}')
 
+    # everything below measures beside the headline figure: --full only
+    extras = args.full and not args.profile_only
     roofline, kernels = None, None
-    if not args.profile_only:
+    if extras:
         model.set_timing(True)
         model.reset_stats()
         step()
@@ -719,19 +765,19 @@ def main():
         roofline['mfma_by_precision'] = mfma_fracs(rp_name, cells, roofline['ms_per_launch'])
 
     distributed = None
-    if world > 1:
+    if world > 1 and args.full:
         distributed = distributed_report(drv, rg, world, ms, device)
         log(f'distributed: {distributed}')
 
     nl = None
-    if world == 1 and not args.profile_only:
+    if world == 1 and extras:
         nl = device_nl_timing(box, device)
         log(f'neighbour list: device {nl["device_ms"]} ms, host {nl["host_ms"]} ms')
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and world == 1 and not args.profile_only:
+    if rank == 0 and not args.no_cpu_baseline and world == 1 and extras:
         cpu = cpu_baseline(args.cpu_seconds, args.cpu_cells, model_dir)
     fine_tune = None
-    if world == 1 and not args.profile_only and not args.no_fine_tune and model_dir is None:
+    if world == 1 and extras and not args.no_fine_tune and model_dir is None:
         # BASELINE config 5 measured in the same run (bench_train.py's step,
         # same recipe and timing contract): the driver records it with the line
         import bench_train

@@ -76,7 +76,7 @@ def test_bench_gpus_2_without_launcher():
            if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
                         '--same-device', '--steps', '2', '--warmup', '1', '--cells', '6',
-                        '--no-cpu-baseline'], cwd=ROOT, env=env, capture_output=True,
+                        '--full', '--no-cpu-baseline'], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

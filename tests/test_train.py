@@ -10,6 +10,7 @@ fine-tuning log), the second-order derivative chain of conv_ops, and the
 data-parallel gradient averaging (gloo, world_size 2).  The HIP kernels are
 compared with the same double in tests/test_gpu_train.py.
 """
+import hashlib
 import json
 import math
 import os
@@ -28,7 +29,6 @@ from sevennet_finetuning_amd.nn import SevenNetTrainable
 from sevennet_finetuning_amd.structures import diamond_primitive, mixed_symbols
 
 SYMS = load_manifest_symbols()
-REF_FT = '/root/reference/example_inputs/fine_tuning/estimate_Fisher'
 
 
 @pytest.fixture(scope='module')
@@ -113,20 +113,26 @@ def test_parameters_live_in_one_buffer(model64):
     assert model64.grads_in_flat_buffer()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_FT), reason='reference fixtures absent')
 def test_parameter_names_match_reference_fisher(model64):
-    fisher = torch.load(os.path.join(REF_FT, 'fisher_sevenn.pt'), weights_only=True,
-                        map_location='cpu')
-    opt = torch.load(os.path.join(REF_FT, 'opt_params_sevenn.pt'), weights_only=True,
-                     map_location='cpu')
+    """Against the reference's estimate_Fisher state dicts (fisher_sevenn.pt,
+    opt_params_sevenn.pt) as golden/ft_fisher_opt.npz keeps them
+    (tools/make_train_golden.py): names and shapes of both, each optimum's
+    SHA-256, and the head of each Fisher tensor, tiled here to its shape."""
+    gold = np.load(os.path.join(GOLD, 'ft_fisher_opt.npz'))
+    meta = json.loads(str(gold['meta']))
     names = dict(model64.named_parameters())
-    assert set(fisher) == set(opt) == set(names)
+    assert set(meta['fisher_names']) == set(meta['opt_names']) == set(names)
+    fisher, opt = {}, {}
     for k, p in names.items():
-        assert tuple(fisher[k].shape) == tuple(p.shape) == tuple(opt[k].shape)
+        m = meta['params'][k]
+        assert tuple(m['fisher_shape']) == tuple(p.shape) == tuple(m['opt_shape'])
         # the converted weights are the reference's optimum bit for bit
-        assert torch.equal(p.detach().to(torch.float32), opt[k])
-    ewc = train.EWCLoss({k: v.double() for k, v in fisher.items()},
-                        {k: v.double() for k, v in opt.items()})
+        w = p.detach().to(torch.float32).contiguous()
+        assert torch.equal(w.double(), p.detach().double())
+        assert hashlib.sha256(w.numpy().astype('<f4').tobytes()).hexdigest() == m['opt_sha256']
+        opt[k] = w.double()
+        fisher[k] = torch.from_numpy(np.resize(gold['fisher_head/' + k], tuple(p.shape))).double()
+    ewc = train.EWCLoss(fisher, opt)
     assert float(ewc.get_loss({}, model64)) == 0.0
 
 

@@ -24,14 +24,14 @@ for s in "$@"; do
     parity) run parity 600 python -u -m pytest tests/test_gpu_parity.py -x -q --timeout 300 --timeout-method thread ;;
     graphs) run graphs 600 python -u -m pytest tests/test_gpu_train.py -x -q --timeout 300 --timeout-method thread -k "graph or rejects" ;;
     tests) run tests 1100 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread ;;
-    bench) run bench 300 python bench.py --steps 5 --warmup 1 --no-cpu-baseline ;;
-    benchfull) run benchfull 400 python bench.py ;;
-    bv_*) v=${s#bv_}; run bench_$v 300 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-parity-check ;;
+    bench) run bench 300 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline ;;
+    benchfull) run benchfull 400 python bench.py --full ;;
+    bv_*) v=${s#bv_}; run bench_$v 300 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-parity-check ;;
     pv_*) v=${s#pv_}; run parity_$v 600 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python -u -m pytest tests/test_gpu_parity.py -x -q --timeout 300 --timeout-method thread ;;
     fv_*) v=${s#fv_}; run full_$v 600 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python -u -m pytest tests/test_gpu_fullsize.py -x -q --timeout 400 --timeout-method thread -k "v1 or determin or supercell"
           run family_$v 600 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python -u -m pytest tests/test_gpu_family.py -x -q --timeout 400 --timeout-method thread ;;
     nve) run nve 900 python -u tools/nve_drift.py --cells 3 --steps 2000 --dt 1.0 --temp 600 ;;
-    hfo2) run bench_hfo2 600 python bench.py --system hfo2 --steps 5 --warmup 1 --no-cpu-baseline ;;
+    hfo2) run bench_hfo2 600 python bench.py --full --system hfo2 --steps 5 --warmup 1 --no-cpu-baseline ;;
     rankemu) run rankemu 900 python -u bench.py --rank-emulation 0,7 --steps 3 --warmup 1 ;;
     newtests) run newtests 900 python -u -m pytest tests/test_gpu_generic.py tests/test_gpu_train.py -x -q --timeout 300 --timeout-method thread -k "bias_and_fcn or workspace or rejects" ;;
     nvetest) run nvetest 600 python -u -m pytest tests/test_gpu_native.py -x -q -s --timeout 400 --timeout-method thread -k nve_drift ;;
