@@ -1,9 +1,11 @@
 """Build libe3gnn_hip.so in-tree for gfx950 (hipcc cross-compiles without a GPU).
 
     python -m sevennet_finetuning_amd.build_lib [--force]
+    python -m sevennet_finetuning_amd.build_lib --out PATH -DSWITCH[=V] ...   (a variant)
 
 The library is the product: the Python surface of this package only loads it
-(``_lib.py``) and fails loudly when it is missing.
+(``_lib.py``) and fails loudly when it is missing.  A variant (``SWITCHES``)
+is always written to a path of its own.
 """
 import os
 import subprocess
@@ -32,9 +34,24 @@ def _deps_mtime():
     return max(os.path.getmtime(f) for f in files)
 
 
+# the only compile-time switches of csrc/ (fused.hip): the diagnostic stamps
+# and the six-product reference forms
+SWITCHES = ('E3GNN_STAMPS', 'E3GNN_STAMPS_FWD', 'E3GNN_DH2_X3', 'E3GNN_BWD_W_X3', 'E3GNN_CHAIN_X3')
+
+
+def _check_defines(out, defines):
+    """A variant never becomes the product, and never carries a name no source reads."""
+    if defines and out is None:
+        raise ValueError('defines build a variant: give it a path of its own (out / --out)')
+    for d in defines:
+        if d.split('=', 1)[0] not in SWITCHES:
+            raise ValueError(f'unknown switch {d!r}: the switches are {", ".join(SWITCHES)}')
+
+
 def build(force=False, verbose=False, out=None, defines=()):
-    """Compile and link the library (``out``: another path, for A/B variants
-    built with extra ``-D`` ``defines``)."""
+    """Compile and link the library (``out``: another path, required for the
+    variants built with extra ``-D`` ``defines``, each one of ``SWITCHES``)."""
+    _check_defines(out, defines)
     lib = out or LIB
     if not force and os.path.exists(lib) and os.path.getmtime(lib) >= _deps_mtime():
         if out is None:

@@ -377,9 +377,9 @@ __device__ __forceinline__ void mlp_pre(const WRes& R, const float* __restrict__
   mlp_chain(R, b, lane, m);
 }
 
-// both tiles of a forward pass (E3GNN_FWD_CHAIN2): layer 1's W1 operand
-// blocks loaded once for the two tiles' products (the same six products per
-// tile as mlp_chain, the same sums)
+// both tiles of a forward pass: layer 1's W1 operand blocks loaded once for
+// the two tiles' products (the same six products per tile as mlp_chain, the
+// same sums)
 __device__ __forceinline__ void mlp_pre2(const WRes& R, const float* __restrict__ emb, int e0, int e1,
                                          bool two, int lane, f32x4 (&a2)[2][4]) {
   const int g = lane >> 4, c = lane & 15;
@@ -683,20 +683,14 @@ __device__ __forceinline__ void load_tile_edges(const int* __restrict__ nbr,
 // block (128 input channels) fits three, the others two
 // row sums over the four lane groups as groups of permlane swaps (the
 // forward's D3 values per path, the lock-step backward's 8 dE/dY values per
-// edge; E3GNN_ROWSUM_GROUPED, default) instead of one hazard-padded pair of
-// swaps per value: middle forward 9.21 -> 9.01-9.11 ms for the three launches,
-// same box (profiles/r06_s20_*); in the last block's backward it measured
-// neutral to slower and stays per value
-#ifndef E3GNN_ROWSUM_GROUPED
-#define E3GNN_ROWSUM_GROUPED 1
-#endif
-// the forward pass's two tiles through the radial MLP together, each W1
-// operand block loaded once for both (E3GNN_FWD_CHAIN2; same products, same
-// bits): last-block forward 1.05-1.06 -> 1.00-1.01 ms, middle 9.13 -> 9.02 ms
+// edge) instead of one hazard-padded pair of swaps per value: middle forward
+// 9.21 -> 9.01-9.11 ms for the three launches, same box (profiles/r06_s20_*);
+// in the last block's backward it measured neutral to slower and stays per
+// value
+// the middle and last blocks' two tiles go through the radial MLP together,
+// each W1 operand block loaded once for both (same products, same bits):
+// last-block forward 1.05-1.06 -> 1.00-1.01 ms, middle 9.13 -> 9.02 ms
 // averaged over two runs each (noisy box; profiles/r06_s23_*)
-#ifndef E3GNN_FWD_CHAIN2
-#define E3GNN_FWD_CHAIN2 1
-#endif
 template <class L>
 struct Fwd2Waves {
   static constexpr int v = L::KIND == 0 ? 3 : 2;
@@ -709,7 +703,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd2Waves<L
   __shared__ float lds[4][2][160];
   __shared__ __attribute__((aligned(16))) float aggl[4][L::DM];
   const int wid = threadIdx.x >> 6;
-  const int c = __builtin_amdgcn_readfirstlane(c_begin + xcd_block() * 4 + wid);
+  const int c = __builtin_amdgcn_readfirstlane(c_begin + blockIdx.x * 4 + wid);
   if (c >= c_end) return;
   float* acl = aggl[wid];
   const int lane = threadIdx.x & 63, g = lane >> 4, col = lane & 15;
@@ -743,7 +737,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd2Waves<L
     auto load_group = [&](auto Iq, int jq) { load_rows(Iq, jq, 0, xpf); };
     load_group(std::integral_constant<int, first_I<L>()>{}, 0);
     Op3 hq[2];
-    if constexpr (E3GNN_FWD_CHAIN2 && L::KIND != 0) {   // (the first block: three waves, no room)
+    if constexpr (L::KIND != 0) {   // (the first block: three waves, no room)
       f32x4 a2[2][4];
       mlp_pre2(R, emb, e0, end, two, lane, a2);
 #pragma unroll
@@ -808,11 +802,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd2Waves<L
               tp_acc4<p.l1, p.l2, p.l3>(x[0], lds[wid][0] + 4 * g * 9 + yoff(p.l2), 9, wv0, acc);
               if (two) tp_acc4<p.l1, p.l2, p.l3>(x[1], lds[wid][1] + 4 * g * 9 + yoff(p.l2), 9, wv1, acc);
               if constexpr (STAMPED) STAMP(3);   // tensor product
-              if constexpr (E3GNN_ROWSUM_GROUPED) sum_rows4_n<D3>(acc);
+              sum_rows4_n<D3>(acc);
 #pragma unroll
               for (int k = 0; k < D3; ++k) {
-                float v = acc[k];
-                v = (E3GNN_ROWSUM_GROUPED ? v : sum_rows4(v)) * rden;
+                const float v = acc[k] * rden;
                 if (g == 0) {
                   float* a = acl + p.moff + (16 * j + col) * D3 + k;
                   *a = first_tile ? v : *a + v;
@@ -897,18 +890,12 @@ __device__ __forceinline__ void load_gm(float* gmN, __amdgpu_buffer_rsrc_t Rg, i
 __device__ __forceinline__ void mlp_bwd_chain_ids(const WRes& R, const float* __restrict__ emb, int er,
                                                   int lane, const f32x4 (&dh2)[4],
                                                   float* __restrict__ demb, const float* dold = nullptr,
-                                                  const float* bk = nullptr, const f32x4* a2k = nullptr,
-                                                  const f32x4* a1k = nullptr) {
+                                                  const float* bk = nullptr, const f32x4* a2k = nullptr) {
   const int g = lane >> 4;
   MlpT m;
   if (a2k) {   // (the tile start's layer-1 pre-activations kept: layer 0 only)
-    if (a1k) {   // (and layer 0's: nothing recomputed)
-#pragma unroll
-      for (int bb = 0; bb < 4; ++bb) m.a1[bb] = a1k[bb];
-    } else {
-      const float b[2] = {bk[0], bk[1]};
-      mlp_layer0(R, b, lane, m.a1);
-    }
+    const float b[2] = {bk[0], bk[1]};
+    mlp_layer0(R, b, lane, m.a1);
 #pragma unroll
     for (int bb = 0; bb < 4; ++bb) m.a2[bb] = a2k[bb];
   } else {
@@ -963,10 +950,9 @@ __device__ __forceinline__ void mlp_bwd_chain_ids(const WRes& R, const float* __
 __device__ __forceinline__ void mlp_bwd_chain(const WRes& R, const float* __restrict__ emb, int e0,
                                               int end, int lane, const f32x4 (&dh2)[4],
                                               float* __restrict__ demb, const float* dold = nullptr,
-                                              const float* bk = nullptr, const f32x4* a2k = nullptr,
-                                              const f32x4* a1k = nullptr) {
+                                              const float* bk = nullptr, const f32x4* a2k = nullptr) {
   const int e = e0 + (lane & 15);
-  mlp_bwd_chain_ids(R, emb, e < end ? e : -1, lane, dh2, demb, dold, bk, a2k, a1k);
+  mlp_bwd_chain_ids(R, emb, e < end ? e : -1, lane, dh2, demb, dold, bk, a2k);
 }
 
 // Backward of the last block (224 message channels), one wave per NEIGHBOUR
@@ -995,153 +981,65 @@ __device__ __forceinline__ void mlp_bwd_chain(const WRes& R, const float* __rest
 #ifndef E3GNN_DH2_X3
 #define E3GNN_DH2_X3 1
 #endif
-// operand pieces requested before the MFMAs that consume them (default;
-// =0 the per-block interleaved order the compiler chose): the middle
-// backward's pair images from LDS (E3GNN_LDS_EARLY: 5.56 -> 5.46 ms per launch,
-// same box) and the last block's dH2 pieces from L2 (E3GNN_NBR_EARLY: 2.21 ->
-// 2.10 ms; profiles/r06_s10_*)
+// operand pieces are requested before the MFMAs that consume them, not in the
+// per-block interleaved order the compiler chose: the middle backward's pair
+// images from LDS (5.56 -> 5.46 ms per launch, same box) and the last block's
+// dH2 pieces from L2 (2.21 -> 2.10 ms; profiles/r06_s10_*)
 // the middle blocks' tile-end read-modify-writes of dE/du and dE/demb: the
-// old values read at the tile start (E3GNN_RMW_PF: 5.39 -> 5.34 ms per launch,
-// same box; profiles/r06_s12_*)
+// old values read at the tile start (5.39 -> 5.34 ms per launch, same box;
+// profiles/r06_s12_*)
 // the middle blocks' tile-start layer-1 pre-activations (a2) and embedding
 // values kept to the tile end, whose MLP chain backward then recomputes layer
-// 0 only (E3GNN_KEEP_A2: 5.38-5.39 -> 5.21-5.27 ms per launch, same box;
-// profiles/r06_s16_*)
-#ifndef E3GNN_KEEP_A2
-#define E3GNN_KEEP_A2 1
-#endif
-#ifndef E3GNN_RMW_PF
-#define E3GNN_RMW_PF 1
-#endif
-#ifndef E3GNN_LDS_EARLY
-#define E3GNN_LDS_EARLY 1
-#endif
-// the same for the last block's per-pass dE/du and dE/demb (E3GNN_NBR_RMW_PF:
-// 2.13 -> 2.09-2.12 ms, same box; profiles/r06_s12_*)
-#ifndef E3GNN_NBR_RMW_PF
-#define E3GNN_NBR_RMW_PF 1
-#endif
-#ifndef E3GNN_NBR_EARLY
-#define E3GNN_NBR_EARLY 1
-#endif
+// 0 only (5.38-5.39 -> 5.21-5.27 ms per launch, same box; profiles/r06_s16_*;
+// keeping layer 0's as well measured slower)
+// the same old-value reads for the last block's per-pass dE/du and dE/demb
+// (2.13 -> 2.09-2.12 ms, same box; profiles/r06_s12_*)
 constexpr int LS_BLK = 6144;            // bytes of one w2v column block (3 pieces x 2 halves x 1 KB)
 constexpr int LS_PAIR_W = 2 * LS_BLK;   // the pair's two w-recompute operand blocks
 constexpr int LS_PAIR_D = 12288;        // the pair's dH2 operand (w2d: 3 pieces x 4 bh x 1 KB)
 
-// the same product with the pair's W2 pieces read from global memory (L2: every
-// wave of the launch reads the same operand; w2d order, MlpW::w2d): per hidden
-// block the three pieces are loaded right before its six MFMAs
-__device__ __forceinline__ void dh2_pair_g(f32x4 (&dh2)[4], const float (&da)[4], const float (&db)[4],
-                                           __amdgpu_buffer_rsrc_t w2d, int pair, int lane) {
-  if constexpr (E3GNN_DH2_X3) {   // three products (see dh2_pair)
-    bf16x8 d[2];
-    {
-      float v[8];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) v[t] = t < 4 ? da[t] : db[t - 4];
-      split2x8(v, d);
-    }
-#pragma unroll
-    for (int bh = 0; bh < 4; ++bh) {
-      bf16x8 a[2];
-#pragma unroll
-      for (int pc = 0; pc < 2; ++pc)
-        a[pc] = __builtin_bit_cast(
-            bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2d, lane * 16, pair * LS_PAIR_D + (pc * 4 + bh) * 1024, 0));
-      dh2[bh] = mfma16(a[1], d[0], dh2[bh]);
-      dh2[bh] = mfma16(a[0], d[1], dh2[bh]);
-      dh2[bh] = mfma16(a[0], d[0], dh2[bh]);
-    }
-    return;
-  }
-  bf16x8 d[3];
-  {
-    float v[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) v[t] = t < 4 ? da[t] : db[t - 4];
-    split3x8(v, d);
-  }
-  constexpr int I[6] = {2, 1, 0, 1, 0, 0}, J[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-  for (int bh = 0; bh < 4; ++bh) {
-    bf16x8 a[3];
-#pragma unroll
-    for (int pc = 0; pc < 3; ++pc)
-      a[pc] = __builtin_bit_cast(
-          bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2d, lane * 16, pair * LS_PAIR_D + (pc * 4 + bh) * 1024, 0));
-#pragma unroll
-    for (int q = 0; q < 6; ++q) dh2[bh] = mfma16(a[I[q]], d[J[q]], dh2[bh]);
-  }
-}
-
-// both tiles of a pass at once: each W2 piece block is loaded once and feeds
-// the two tiles' products (the one-tile form above loaded the pair's pieces
-// per tile: half of the last block's dH2 operand stream)
+// dH2^T += W2[:, pair] dw^T on three bf16 products with the pair's W2 pieces
+// read from global memory (L2: every wave of the launch reads the same
+// operand; w2d order, MlpW::w2d; see dh2_pair for the operand layout), both
+// tiles of a pass at once: each W2 piece block is loaded once and feeds the
+// two tiles' products (per tile it was twice the last block's dH2 operand
+// stream)
 __device__ __forceinline__ void dh2_pair_g2(f32x4 (&dh2)[2][4], const float (&dp)[2][4], const float (&dr)[2][4],
                                             bool two, __amdgpu_buffer_rsrc_t w2d, int pair, int lane) {
-  constexpr int NPC = E3GNN_DH2_X3 ? 2 : 3;
-  bf16x8 d[2][3];
+  bf16x8 d[2][2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     float v[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) v[t] = t < 4 ? dp[u][t] : dr[u][t - 4];
-    if constexpr (NPC == 2) {
-      bf16x8 e[2];
-      split2x8(v, e);
-      d[u][0] = e[0];
-      d[u][1] = e[1];
-    } else {
-      split3x8(v, d[u]);
-    }
+    split2x8(v, d[u]);
   }
-#if E3GNN_NBR_EARLY
   // every piece of the pair requested first (one L2 latency per pair)
-  bf16x8 aa[4][NPC];
+  bf16x8 a[4][2];
 #pragma unroll
   for (int bh = 0; bh < 4; ++bh)
 #pragma unroll
-    for (int pc = 0; pc < NPC; ++pc)
-      aa[bh][pc] = __builtin_bit_cast(
+    for (int pc = 0; pc < 2; ++pc)
+      a[bh][pc] = __builtin_bit_cast(
           bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2d, lane * 16, pair * LS_PAIR_D + (pc * 4 + bh) * 1024, 0));
-#endif
 #pragma unroll
   for (int bh = 0; bh < 4; ++bh) {
-    bf16x8 a[NPC];
-#pragma unroll
-    for (int pc = 0; pc < NPC; ++pc)
-#if E3GNN_NBR_EARLY
-      a[pc] = aa[bh][pc];
-#else
-      a[pc] = __builtin_bit_cast(
-          bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2d, lane * 16, pair * LS_PAIR_D + (pc * 4 + bh) * 1024, 0));
-#endif
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       if (u == 1 && !two) break;
-      if constexpr (NPC == 2) {
-        dh2[u][bh] = mfma16(a[1], d[u][0], dh2[u][bh]);
-        dh2[u][bh] = mfma16(a[0], d[u][1], dh2[u][bh]);
-        dh2[u][bh] = mfma16(a[0], d[u][0], dh2[u][bh]);
-      } else {
-        constexpr int I[6] = {2, 1, 0, 1, 0, 0}, J[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-        for (int q = 0; q < 6; ++q) dh2[u][bh] = mfma16(a[I[q]], d[u][J[q]], dh2[u][bh]);
-      }
+      dh2[u][bh] = mfma16(a[bh][1], d[u][0], dh2[u][bh]);
+      dh2[u][bh] = mfma16(a[bh][0], d[u][1], dh2[u][bh]);
+      dh2[u][bh] = mfma16(a[bh][0], d[u][0], dh2[u][bh]);
     }
   }
 }
-#ifndef E3GNN_NBR_DH2_SHARED
-#define E3GNN_NBR_DH2_SHARED 1
-#endif
 
 // the last block's dH2 on bf16 MFMA from global (L2) W2 pieces: with the
 // three-product form its operand traffic equals the f32 form's (two pieces x 4
 // hidden blocks per pair) and the MFMA cycles drop ~5x (2.60 -> 2.41 ms, same
-// box); the six-product form (E3GNN_DH2_X3=0) measured slower than f32
-#ifndef E3GNN_NBR_DH2_BF16
-#define E3GNN_NBR_DH2_BF16 E3GNN_DH2_X3
-#endif
+// box); the six-product form measured slower than f32, so the six-product
+// build (E3GNN_DH2_X3=0) takes the f32 form there
+constexpr bool NBR_DH2_BF16 = E3GNN_DH2_X3 != 0;
 template <class L>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_conv_bwd_nbr(
     const int* __restrict__ src_ptr, const int* __restrict__ src_perm, const int* __restrict__ center,
@@ -1150,7 +1048,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     int r_begin, int r_end, float* __restrict__ demb) {
   __shared__ __attribute__((aligned(16))) float lds[4][L::DX];
   const int wid = threadIdx.x >> 6;
-  const int jn = __builtin_amdgcn_readfirstlane(r_begin + xcd_block() * 4 + wid);
+  const int jn = __builtin_amdgcn_readfirstlane(r_begin + blockIdx.x * 4 + wid);
   if (jn >= r_end) return;
   float* dacc = lds[wid];
   const int lane = threadIdx.x & 63, g = lane >> 4, col = lane & 15;
@@ -1167,7 +1065,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     load_w2b(wq, R.w2b, lane, L::P[0].woff);
     int er[2], vg[2];
     float y[2][9];
-    // E3GNN_NBR_RMW_PF: the pass end's dE/du and dE/demb old values, read here
+    // the pass end's dE/du and dE/demb old values, read here
     float gu_old[2][3], de_old[2][4];
     Op3 hq[2];
 #pragma unroll
@@ -1177,12 +1075,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       vg[u] = (er[u] >= 0 ? center[er[u]] * L::DM : n_centers * L::DM) * 4;
 #pragma unroll
       for (int k = 0; k < 9; ++k) y[u][k] = er[u] >= 0 ? Y[(int64_t)er[u] * 9 + k] : 0.f;
-      if constexpr (E3GNN_NBR_RMW_PF) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) gu_old[u][k] = (g == 0 && er[u] >= 0) ? dgu[(int64_t)er[u] * 3 + k] : 0.f;
+      for (int k = 0; k < 3; ++k) gu_old[u][k] = (g == 0 && er[u] >= 0) ? dgu[(int64_t)er[u] * 3 + k] : 0.f;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) de_old[u][k] = (g < 2 && er[u] >= 0) ? demb[(int64_t)er[u] * 8 + 4 * g + k] : 0.f;
-      }
+      for (int k = 0; k < 4; ++k) de_old[u][k] = (g < 2 && er[u] >= 0) ? demb[(int64_t)er[u] * 8 + 4 * g + k] : 0.f;
       if (u == 1 && !two) continue;
       float b[2];
 #pragma unroll
@@ -1201,9 +1097,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int u = 0; u < 2; ++u)
 #pragma unroll
       for (int bb = 0; bb < 4; ++bb) dh2[u][bb] = zero4();
-#if E3GNN_NBR_DH2_BF16
-    float dwp[2][4];   // dE/dw of the block pair's first block, per tile
-#endif
+    float dwp[2][4];   // dE/dw of the block pair's first block, per tile (the bf16 dH2 form)
     int nb = 0;
     constexpr int NBLK = L::W / 16;
     f32x4 wcur[2], wnxt[2] = {zero4(), zero4()};
@@ -1235,17 +1129,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
               float gm[2][4 * D3];
               load_gm<L, pi>(gm[0], Rg, vg[0], g, jj);
               load_gm<L, pi>(gm[1], Rg, vg[1], g, jj);
-#if !E3GNN_NBR_DH2_BF16
-              f32x4 bq[4];
-              load_w2q(bq, R.w2r, lane, p.woff + 16 * jj);
-#endif
+              f32x4 bq[4];   // W2 blocks of the f32 dH2 form
+              if constexpr (!NBR_DH2_BF16) load_w2q(bq, R.w2r, lane, p.woff + 16 * jj);
               f32x4 wv[2] = {wcur[0], wcur[1]};
               if (nb + 1 < NBLK) {
                 wnxt[0] = w2_block_bwd<false>(hq[0], wq);
                 wnxt[1] = two ? w2_block_bwd<false>(hq[1], wq) : zero4();
               }
               if (nb + 2 < NBLK) load_w2b(wq, R.w2v, lane, 16 * (nb + 2));
-              float dwr2[2][4];   // both tiles' dE/dw (the shared dH2 form)
+              float dwr2[2][4];   // both tiles' dE/dw (the bf16 dH2 form)
 #pragma unroll
               for (int u = 0; u < 2; ++u) {
                 if (u == 1 && !two) break;
@@ -1266,42 +1158,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                   pin<D1>(dx + r * D1);
                   pin<8>(dYa[u] + 1);
                 }
-#if E3GNN_NBR_DH2_BF16 && E3GNN_NBR_DH2_SHARED
+                if constexpr (NBR_DH2_BF16) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) dwr2[u][r] = u == 1 && !two ? 0.f : dwr[r];
-#elif E3GNN_NBR_DH2_BF16
-                // dH2^T += W2[:, pair] dw^T on bf16x6 over the block pair (K = 32
-                // channels: the pair's first block is held in dwp)
+                  for (int r = 0; r < 4; ++r) dwr2[u][r] = u == 1 && !two ? 0.f : dwr[r];
+                } else {
+                  // dH2^T += W2[:, block] dw^T: k = lane group g, channel 4g + r
+#pragma unroll
+                  for (int bh = 0; bh < 4; ++bh)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) dh2[u][bh] = mfma(bq[bh][r], dwr[r], dh2[u][bh]);
+                }
+              }
+              if constexpr (NBR_DH2_BF16) {
+                if (!two) {
+#pragma unroll
+                  for (int r = 0; r < 4; ++r) dwr2[1][r] = 0.f;
+                }
+                // dH2^T += W2[:, pair] dw^T over the block pair for both tiles,
+                // each W2 piece loaded once (the pair's first block held in dwp)
                 if (nb & 1) {
-                  dh2_pair_g(dh2[u], dwp[u], dwr, R.w2d, nb >> 1, lane);
+                  dh2_pair_g2(dh2, dwp, dwr2, two, R.w2d, nb >> 1, lane);
                 } else {
 #pragma unroll
-                  for (int r = 0; r < 4; ++r) dwp[u][r] = dwr[r];
+                  for (int u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) dwp[u][r] = dwr2[u][r];
                 }
-#else
-                // dH2^T += W2[:, block] dw^T: k = lane group g, channel 4g + r
-#pragma unroll
-                for (int bh = 0; bh < 4; ++bh)
-#pragma unroll
-                  for (int r = 0; r < 4; ++r) dh2[u][bh] = mfma(bq[bh][r], dwr[r], dh2[u][bh]);
-#endif
               }
-#if E3GNN_NBR_DH2_BF16 && E3GNN_NBR_DH2_SHARED
-              if (!two) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) dwr2[1][r] = 0.f;
-              }
-              // dH2^T += W2[:, pair] dw^T over the block pair for both tiles,
-              // each W2 piece loaded once (the pair's first block held in dwp)
-              if (nb & 1) {
-                dh2_pair_g2(dh2, dwp, dwr2, two, R.w2d, nb >> 1, lane);
-              } else {
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                  for (int r = 0; r < 4; ++r) dwp[u][r] = dwr2[u][r];
-              }
-#endif
               pin<4 * D1>(dx);
               wcur[0] = wnxt[0];
               wcur[1] = wnxt[1];
@@ -1337,18 +1220,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const float gy = s3 * d[1] + c15 * (ux * d[4] + uz * d[6]) + 2.f * s5 * uy * d[5];
         const float gz = s3 * d[2] + c15 * (ux * d[3] + uy * d[6]) - s5 * uz * d[5] + c15 * uz * d[7];
         float* o = dgu + (int64_t)er[u] * 3;
-        if constexpr (E3GNN_NBR_RMW_PF) {
-          o[0] = gu_old[u][0] + gx;
-          o[1] = gu_old[u][1] + gy;
-          o[2] = gu_old[u][2] + gz;
-        } else {
-          o[0] += gx;
-          o[1] += gy;
-          o[2] += gz;
-        }
+        o[0] = gu_old[u][0] + gx;
+        o[1] = gu_old[u][1] + gy;
+        o[2] = gu_old[u][2] + gz;
       }
       phase();
-      mlp_bwd_chain_ids(R, emb, er[u], lane, dh2[u], demb, E3GNN_NBR_RMW_PF ? de_old[u] : nullptr);
+      mlp_bwd_chain_ids(R, emb, er[u], lane, dh2[u], demb, de_old[u]);
     }
   }
   phase();
@@ -1371,12 +1248,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 // The staged image holds only the pieces the backward's products read: with
 // the three-product forms (E3GNN_BWD_W_X3, E3GNN_DH2_X3) pieces 0 and 1 of
-// each operand, 16 KB per pair instead of 24 (E3GNN_LS_LEAN=0: all three)
-#ifndef E3GNN_LS_LEAN
-#define E3GNN_LS_LEAN 1
-#endif
-constexpr int LS_WPC = (E3GNN_LS_LEAN && E3GNN_BWD_W_X3) ? 2 : 3;   // staged pieces of a w-recompute block
-constexpr int LS_DPC = (E3GNN_LS_LEAN && E3GNN_DH2_X3) ? 2 : 3;     // of the pair's dH2 operand
+// each operand, 16 KB per pair instead of 24
+constexpr int LS_WPC = E3GNN_BWD_W_X3 ? 2 : 3;   // staged pieces of a w-recompute block
+constexpr int LS_DPC = E3GNN_DH2_X3 ? 2 : 3;     // of the pair's dH2 operand
 constexpr int LS_IBLK = LS_WPC * 2048;   // image bytes of one w-recompute block (pieces x 2 halves x 1 KB)
 constexpr int LS_IW = 2 * LS_IBLK;       // the pair's w-recompute part
 constexpr int LS_IMG = LS_IW + LS_DPC * 4096;   // + the dH2 part (pieces x 4 bh x 1 KB)
@@ -1404,7 +1278,6 @@ __device__ __forceinline__ void dh2_pair(f32x4 (&dh2)[4], const float (&da)[4], 
       for (int t = 0; t < 8; ++t) v[t] = t < 4 ? da[t] : db[t - 4];
       split2x8(v, d);
     }
-#if E3GNN_LDS_EARLY
     // every piece read first, fenced from the MFMAs (one exposed LDS latency
     // for the pair, not one per hidden block)
     bf16x8 a[4][2];
@@ -1420,18 +1293,6 @@ __device__ __forceinline__ void dh2_pair(f32x4 (&dh2)[4], const float (&da)[4], 
       dh2[bh] = mfma16(a[bh][0], d[1], dh2[bh]);
       dh2[bh] = mfma16(a[bh][0], d[0], dh2[bh]);
     }
-#else
-#pragma unroll
-    for (int bh = 0; bh < 4; ++bh) {
-      bf16x8 a[2];
-#pragma unroll
-      for (int pc = 0; pc < 2; ++pc)
-        a[pc] = *reinterpret_cast<const bf16x8*>(pimg + ((pc * 4 + bh) * 64 + lane) * 16);
-      dh2[bh] = mfma16(a[1], d[0], dh2[bh]);
-      dh2[bh] = mfma16(a[0], d[1], dh2[bh]);
-      dh2[bh] = mfma16(a[0], d[0], dh2[bh]);
-    }
-#endif
     return;
   }
   bf16x8 d[3];
@@ -1454,17 +1315,13 @@ __device__ __forceinline__ void dh2_pair(f32x4 (&dh2)[4], const float (&da)[4], 
 }
 
 // tiles of the workgroup's centres [cb, cb + 4) clipped to c_end: the lock-step
-// loop count (min_one: a centre without edges still has its one (empty) tile)
-__device__ __forceinline__ int ls_tiles(const int* __restrict__ row_ptr, int cb, int c_end,
-                                        bool min_one, int wpg = 4) {
+// loop count
+__device__ __forceinline__ int ls_tiles(const int* __restrict__ row_ptr, int cb, int c_end) {
   int T = 0;
 #pragma unroll
-  for (int w = 0; w < wpg; ++w) {
+  for (int w = 0; w < 4; ++w) {
     const int cc = cb + w;
-    if (cc < c_end) {
-      const int t = (row_ptr[cc + 1] - row_ptr[cc] + 15) >> 4;
-      T = max(T, min_one ? max(t, 1) : t);
-    }
+    if (cc < c_end) T = max(T, (row_ptr[cc + 1] - row_ptr[cc] + 15) >> 4);
   }
   return __builtin_amdgcn_readfirstlane(T);
 }
@@ -1478,115 +1335,56 @@ __device__ __forceinline__ int ls_tiles(const int* __restrict__ row_ptr, int cb,
 // 42 KB of LDS per workgroup) runs three (168 VGPRs with a few spills
 // measured 2.57 -> 2.27 ms against two), the middle blocks two (225 VGPRs;
 // their 80.9 KB of LDS allows no more)
-#ifndef E3GNN_LS_FIRST_WAVES
-#define E3GNN_LS_FIRST_WAVES 3
-#endif
 template <class L>
 struct BwdLsWaves {
-  static constexpr int v = L::KIND == 0 ? E3GNN_LS_FIRST_WAVES : 2;
+  static constexpr int v = L::KIND == 0 ? 3 : 2;
 };
-// centres (waves) per workgroup: 4; E3GNN_BWD_WPG = 8 (A/B) gives the middle
-// block one 8-wave workgroup per CU sharing each staged W2 pair (124 KB LDS)
-#ifndef E3GNN_BWD_WPG
-#define E3GNN_BWD_WPG 4
-#endif
+// centres (waves) per workgroup (one 8-wave workgroup per CU sharing each
+// staged W2 pair, 124 KB of LDS, measured slower for the middle block)
+constexpr int LS_WPG = 4;
+// Double-buffered staging where two images fit (the middle blocks: backward
+// 5.66 -> 5.53 ms per launch against one image, same box): the pair's pieces
+// are loaded into registers a pair ahead (loads the compiler counts, so its
+// waits leave the neighbour-row prefetch and the dE/dx stores in flight) and
+// written into one of TWO images before the pair's ONE barrier -- the other
+// image is the one the previous pair read, retired by the previous pair's
+// barrier.  The two images need 16 KB more LDS; in the middle blocks the
+// 0e x 0e -> 0e path's dE/dagg (C0 floats, moff 0) is then read from L2 with
+// the neighbour-row prefetch instead of staged, so two workgroups still fit a
+// CU (2 x 80.9 KB of 160 KB).  Elsewhere (and with the three-piece images of
+// the six-product build, which never fit twice): one image, written between
+// two barriers per pair.  Writing the images by LDS-DMA straight from L2 was
+// measured and rejected (5.68 -> 5.77 ms: its explicit wait before the barrier
+// drains every load and store in flight).
 template <class L>
-struct BwdWpg {
-  static constexpr int v = L::KIND == 1 ? E3GNN_BWD_WPG : 4;
+struct LsTwoImages {
+  static constexpr bool lean = LS_WPC == 2 && LS_DPC == 2;   // two-piece images
+  static constexpr int OFF0 = L::KIND == 1 ? L::P[0].mul : 0;   // path 0 (l 0 0 0, moff 0): C0 floats
+  static constexpr int DMS = L::DM - OFF0;                       // staged dE/dagg floats per centre
+  static constexpr int bytes = LS_WPG * DMS * 4 + 2 * LS_IMG;
+  static constexpr bool v = lean && BwdLsWaves<L>::v * bytes <= 163840;
 };
-// LDS-DMA staging (E3GNN_LS_DMA=1; measured and not kept: middle backward
-// 5.68 -> 5.77 ms per launch, the explicit vmcnt(0) before each pair's
-// barrier also drains the neighbour-row prefetch and the dE/dx stores that
-// the compiler's counted waits leave in flight): the pair image is
-// written by global_load_lds_dwordx4 straight from L2 (no staging registers,
-// no ds_write) into one of TWO images, so a pair costs ONE barrier: at pair P
-// each wave waits for its own DMA of P (issued at P - 1), the barrier makes
-// all of P visible and retires every read of P - 1's image, then the DMA of
-// P + 1 goes into that image.  The two images need 16 KB more LDS; in the
-// middle blocks the 0e x 0e -> 0e path's dE/dagg (C0 floats, moff 0) is then
-// read from L2 with the neighbour-row prefetch instead of staged, so two
-// workgroups still fit a CU (2 x 80.9 KB of 160 KB).
-#ifndef E3GNN_LS_DMA
-#define E3GNN_LS_DMA 0
-#endif
-template <class L>
-struct LsDma {
-  static constexpr int WPG = BwdWpg<L>::v;
-  static constexpr bool lean = LS_WPC == 2 && LS_DPC == 2;   // 16 x 1 KB chunks: 4 per wave
-  static constexpr bool drop0 = L::KIND == 1;
-  static constexpr int OFF0 = drop0 ? L::P[0].mul : 0;       // path 0 (l 0 0 0, moff 0): C0 floats
-  static constexpr int DMS = L::DM - OFF0;                    // staged dE/dagg floats per centre
-  static constexpr int bytes = WPG * DMS * 4 + 2 * LS_IMG;
-  static constexpr bool fits = lean && WPG == 4 && BwdLsWaves<L>::v * bytes <= 163840;
-  static constexpr bool v = E3GNN_LS_DMA && fits;
-};
-// Double-buffered REGISTER staging (E3GNN_LS_DB, default on where two images
-// fit: middle backward 5.66 -> 5.53 ms per launch, same box; =0 the single
-// image with two barriers per pair): the same two images and one
-// barrier per pair as the DMA form, the pair's pieces still loaded into
-// registers a pair ahead (loads the compiler counts: no drain of the other
-// loads in flight) and written into the pair's image before the barrier --
-// the other image is the one the previous pair read, retired by the previous
-// pair's barrier.
-#ifndef E3GNN_LS_DB
-#define E3GNN_LS_DB 1
-#endif
-// one wave-instruction of LDS-DMA: 64 lanes x 16 bytes from per-lane global
-// addresses to the wave-uniform LDS byte address lds_dst (+ lane x 16); M0
-// set and restored inside the statement.  hipcc does not count it: the
-// consumer waits with an explicit vmcnt before the barrier that publishes it.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds_dst)
-               : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)p;
-}
-// wave priority around the lock-step backward's MFMA bursts (E3GNN_LS_PRIO:
-// 1 raise it there, 0 never)
-#ifndef E3GNN_LS_PRIO
-#define E3GNN_LS_PRIO 1
-#endif
+// wave priority, raised around the lock-step backward's MFMA bursts
 template <int P>
-__device__ __forceinline__ void ls_prio_c() { __builtin_amdgcn_s_setprio(P); }
-__device__ __forceinline__ void ls_prio(int p) {
-  if constexpr (E3GNN_LS_PRIO) {
-    if (p) ls_prio_c<1>();
-    else ls_prio_c<0>();
-  }
-}
-#ifndef E3GNN_ABL_NOBAR
-#define E3GNN_ABL_NOBAR 0
-#endif
-#ifndef E3GNN_ABL_NOSTAGE
-#define E3GNN_ABL_NOSTAGE 0
-#endif
-#ifndef E3GNN_ABL_XLOCAL
-#define E3GNN_ABL_XLOCAL 0
-#endif
+__device__ __forceinline__ void ls_prio() { __builtin_amdgcn_s_setprio(P); }
 template <class L>
-__global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_eu(BwdLsWaves<L>::v, BwdLsWaves<L>::v))) void k_conv_bwd_ls(
+__global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(BwdLsWaves<L>::v, BwdLsWaves<L>::v))) void k_conv_bwd_ls(
     const int* __restrict__ row_ptr, const int* __restrict__ nbr, const float* __restrict__ emb,
     const float* __restrict__ Y, const float* __restrict__ h, const float* __restrict__ gagg, MlpW W,
     float* __restrict__ dxc, float* __restrict__ dgu, float* __restrict__ demb, int c_begin,
     int c_end, int n_nodes) {
   constexpr int NBLK = L::W / 16, NPAIR = NBLK / 2;
   static_assert(NBLK % 2 == 0, "weight blocks come in pairs");
-  constexpr int WPG = BwdWpg<L>::v, NT = 64 * WPG;
-  // staging pieces (b128) of a pair: the w-recompute operands, then the dH2 ones
-  constexpr int NWP = LS_IW / 16, NST = LS_IMG / 16 / NT, PB = LS_IBLK / 16;
-  static_assert(LS_IMG / 16 % NT == 0 && NWP % 64 == 0 && PB % 64 == 0, "staging pieces per thread");
-  using DM_ = LsDma<L>;
-  constexpr bool DMA = DM_::v;
-  constexpr bool RDB = !DMA && E3GNN_LS_DB && DM_::fits;   // double-buffered register staging
-  constexpr bool TWO = DMA || RDB;                         // two images, one barrier per pair
-  // (the first block at three waves per SIMD: no VGPRs to spare)
-  constexpr bool RPF = E3GNN_RMW_PF && (L::KIND == 1 || BwdLsWaves<L>::v == 2);
-  constexpr bool KA2 = E3GNN_KEEP_A2 && (L::KIND == 1 || BwdLsWaves<L>::v == 2);
-  constexpr int OFF0 = TWO ? DM_::OFF0 : 0, DMS = L::DM - OFF0;   // dE/dagg floats staged per centre
+  constexpr int WPG = LS_WPG, NT = 64 * WPG;
+  // staging pieces (b128) of a pair: the w-recompute operands (NW per thread),
+  // then the dH2 ones (NST per thread in all)
+  constexpr int NWP = LS_IW / 16, NW = NWP / NT, NST = LS_IMG / 16 / NT, PB = LS_IBLK / 16;
+  static_assert(LS_IMG / 16 % NT == 0 && NWP % NT == 0 && PB % 64 == 0, "staging pieces per thread");
+  constexpr bool TWO = LsTwoImages<L>::v;   // two images, one barrier per pair
+  // tile-start values kept in registers to the tile end (the first block at
+  // three waves per SIMD: no VGPRs to spare)
+  constexpr bool KEEP = BwdLsWaves<L>::v == 2;
+  constexpr int OFF0 = TWO ? LsTwoImages<L>::OFF0 : 0, DMS = L::DM - OFF0;   // dE/dagg floats staged per centre
   static_assert(!TWO || (L::P[0].l1 == 0 && L::P[0].l2 == 0 && L::P[0].l3 == 0 && L::P[0].moff == 0 &&
                          OFF0 % 4 == 0), "path 0 is the 0e x 0e -> 0e slice at the row start");
   __shared__ __attribute__((aligned(16))) float smem[WPG * DMS + (TWO ? 2 : 1) * LS_IMG / 4];
@@ -1595,7 +1393,7 @@ __global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_
   const int c = cb + wid;
   const bool valid = c < c_end;
   const int beg = valid ? row_ptr[c] : 0, end = valid ? row_ptr[c + 1] : 0;
-  const int T = ls_tiles(row_ptr, cb, c_end, false, WPG);
+  const int T = ls_tiles(row_ptr, cb, c_end);
   float* dacc = smem + wid * DMS - OFF0;   // dacc[m] for m >= OFF0
   char* img = reinterpret_cast<char*>(smem + WPG * DMS);
   if (valid && end > beg) {
@@ -1603,79 +1401,42 @@ __global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_
     float4* d4 = reinterpret_cast<float4*>(dacc + OFF0);
     for (int k = lane; k < DMS / 4; k += 64) d4[k] = s4[k];
   }
-  // DMA mode: the image the current pair reads (0 / 1), its byte base in LDS,
-  // and path 0's dE/dagg row of this centre through a descriptor (invalid
-  // centres: empty, reads 0)
+  // two images: the one the current pair reads (0 / 1), and path 0's dE/dagg
+  // row of this centre through a descriptor (invalid centres: empty, reads 0)
   int rb = 0;
-  const unsigned img_lds = lds_addr(img);
   const __amdgpu_buffer_rsrc_t Rg0 =
       rsrc_bytes(gagg + (valid ? (int64_t)c * L::DM : 0), valid ? (int64_t)OFF0 * 4 : 0);
-  auto issue_dma = [&](int P, int buf) {
-    // chunk k = 4 wid + i of the image: k < 8 the w-recompute blocks (block
-    // k / 4, piece-half k % 4 of w2v), then the dH2 operand's 8 KB (w2d)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int k = 4 * wid + i;   // wave-uniform
-      const char* src = k < 8 ? reinterpret_cast<const char*>(W.w2v) + (int64_t)P * LS_PAIR_W + (k >> 2) * LS_BLK +
-                                    (k & 3) * 1024
-                              : reinterpret_cast<const char*>(W.w2d) + (int64_t)P * LS_PAIR_D + (k - 8) * 1024;
-      glds16(src + lane * 16, img_lds + buf * LS_IMG + k * 1024);
-    }
-  };
   const WRes R = make_wres(W, L::W);
   const __amdgpu_buffer_rsrc_t Rx = rsrc_bytes(h, (int64_t)n_nodes * L::DX * 4);
   f32x4 st[NST];
   auto issue = [&](int P) {
-#if E3GNN_ABL_NOSTAGE
-    return;
-#endif
     // image piece idx: w-recompute block idx / PB (its first LS_WPC pieces
-    // in the w2v order), then the dH2 operand's first LS_DPC pieces (w2d)
+    // in the w2v order), then the dH2 operand's first LS_DPC pieces (w2d);
+    // each thread's pieces are all W, then all D
     auto wsrc = [&](int idx) { return (idx / PB) * LS_BLK + (idx % PB) * 16; };
-    if constexpr (NWP % NT == 0) {  // (4 waves: each thread's pieces all W, then all D)
-      constexpr int NW = NWP / NT;
 #pragma unroll
-      for (int i = 0; i < NW; ++i) st[i] = ldw4(R.w2v, wsrc(tid + NT * i), P * LS_PAIR_W);
+    for (int i = 0; i < NW; ++i) st[i] = ldw4(R.w2v, wsrc(tid + NT * i), P * LS_PAIR_W);
 #pragma unroll
-      for (int i = NW; i < NST; ++i) st[i] = ldw4(R.w2d, (tid + NT * i - NWP) * 16, P * LS_PAIR_D);
-    } else {
-#pragma unroll
-      for (int i = 0; i < NST; ++i) {
-        const int idx = tid + NT * i;
-        const bool isw = idx < NWP;  // wave-uniform (NWP % 64 == 0)
-        st[i] = isw ? ldw4(R.w2v, wsrc(idx), P * LS_PAIR_W) : ldw4(R.w2d, (idx - NWP) * 16, P * LS_PAIR_D);
-      }
-    }
+    for (int i = NW; i < NST; ++i) st[i] = ldw4(R.w2d, (tid + NT * i - NWP) * 16, P * LS_PAIR_D);
   };
-  // E3GNN_ABL_*: timing-only ablations (results wrong; never the shipped build)
+  // the single image: the previous pair's reads retired, the pair written, published
   auto commit = [&]() {
-#if !E3GNN_ABL_NOBAR
     __syncthreads();
-#endif
-#if !E3GNN_ABL_NOSTAGE
 #pragma unroll
     for (int i = 0; i < NST; ++i) *reinterpret_cast<f32x4*>(img + (tid + NT * i) * 16) = st[i];
-#endif
-#if !E3GNN_ABL_NOBAR
     __syncthreads();
-#endif
   };
   constexpr bool STAMPED = std::is_same<L, LayerMid>::value && !E3GNN_STAMPS_FWD;   // SevenNet-0's
   STAMP_DECL
-  if constexpr (DMA) issue_dma(0, 0);
-  else issue(0);
+  issue(0);
   for (int t = 0; t < T; ++t) {
     if constexpr (STAMPED) STAMP(0);
     const int q0 = beg + 16 * t;
     const bool act = q0 < end;   // wave-uniform
     const int er = (act && q0 + col < end) ? q0 + col : -1;
-#if E3GNN_ABL_XLOCAL   // timing-only: every edge reads the centre's own row (L2-hot)
-    const int vx = (er >= 0 ? c : 0) * L::DX * 4;
-#else
     const int vx = (er >= 0 ? nbr[er] : 0) * L::DX * 4;
-#endif
     float xpf[20];   // the lane's 4 channels x D1 of the next channel group
-    float g0pf[4];   // DMA mode: path 0's dE/dagg of that group (l1 = 0 groups)
+    float g0pf[4];   // two images: path 0's dE/dagg of that group (l1 = 0 groups)
     auto load_group = [&](auto Iq, int jq) {
       constexpr int D1q = 2 * Iq + 1;
       constexpr int XOq = iblock_xoff<L, Iq>();
@@ -1683,9 +1444,10 @@ __global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_
       if constexpr (OFF0 > 0 && Iq == 0) ldv<4>(Rg0, 4 * g * 4, 16 * jq * 4, g0pf);
     };
     float y[9];
-    float gu_old[3] = {0.f, 0.f, 0.f}, de_old[4] = {0.f, 0.f, 0.f, 0.f};   // E3GNN_RMW_PF
-    f32x4 a2k[4];   // E3GNN_KEEP_A2: layer-1 pre-activations of the tile, kept to its end
-    f32x4 a1k[E3GNN_KEEP_A2 >= 2 ? 4 : 1];   // (= 2: layer 0's as well)
+    // KEEP: old values of the tile end's read-modify-writes, and the tile's
+    // layer-1 pre-activations and embedding values
+    float gu_old[3] = {0.f, 0.f, 0.f}, de_old[4] = {0.f, 0.f, 0.f, 0.f};
+    f32x4 a2k[4];
     float bk[2];
     Op3 hq;
     // neighbour rows (lanes without an edge read row 0: harmless, their y
@@ -1705,7 +1467,7 @@ __global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_
       float b[2];
 #pragma unroll
       for (int s = 0; s < 2; ++s) b[s] = er >= 0 ? emb[(int64_t)er * 8 + 4 * s + g] : 0.f;
-      if constexpr (RPF) {
+      if constexpr (KEEP) {
         // the tile end's read-modify-writes (dE/du, dE/demb of the lane's
         // edge): old values read here, their latency under the whole tile
         if (g == 0 && er >= 0) {
@@ -1719,13 +1481,9 @@ __global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_
       }
       MlpT m;
       mlp_chain<CX3>(R, b, lane, m);
-      if constexpr (KA2) {
+      if constexpr (KEEP) {
 #pragma unroll
         for (int bb = 0; bb < 4; ++bb) a2k[bb] = m.a2[bb];
-        if constexpr (E3GNN_KEEP_A2 >= 2) {
-#pragma unroll
-          for (int bb = 0; bb < 4; ++bb) a1k[bb] = m.a1[bb];
-        }
         bk[0] = b[0];
         bk[1] = b[1];
       }
@@ -1782,12 +1540,7 @@ __global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_
                 if constexpr (!ODD) {   // pair start: stage it, fetch the next one
                   if constexpr (STAMPED) STAMP(5);
                   const int nextP = (nb >> 1) + 1 < NPAIR ? (nb >> 1) + 1 : 0;
-                  if constexpr (DMA) {
-                    // this wave's DMA of the pair has landed; after the barrier
-                    // every wave's has, and nobody reads the other image any more
-                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                    issue_dma(nextP, rb ^ 1);
-                  } else if constexpr (RDB) {
+                  if constexpr (TWO) {
                     // this pair's image (the one two pairs back read, retired
                     // by the previous pair's barrier), then the one barrier
 #pragma unroll
@@ -1801,29 +1554,21 @@ __global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_
                   }
                   if constexpr (STAMPED) STAMP(2);   // barriers + staging
                   if (act) {
-                    ls_prio(1);   // MFMA bursts first
-#if E3GNN_LDS_EARLY
+                    ls_prio<1>();   // MFMA bursts first
                     Op3 wq, wq1;   // both blocks' pieces read first
                     lds_op3<LS_WPC>(wq, pimg, lane);
                     lds_op3<LS_WPC>(wq1, pimg + LS_IBLK, lane);
                     phase();
                     wv0 = w2_block_bwd<false>(hq, wq);
                     wv1 = w2_block_bwd<false>(hq, wq1);
-#else
-                    Op3 wq;
-                    lds_op3<LS_WPC>(wq, pimg, lane);
-                    wv0 = w2_block_bwd<false>(hq, wq);
-                    lds_op3<LS_WPC>(wq, pimg + LS_IBLK, lane);
-                    wv1 = w2_block_bwd<false>(hq, wq);
-#endif
-                    ls_prio(0);
+                    ls_prio<0>();
                   }
                   if constexpr (STAMPED) STAMP(3);   // w recompute
                 }
                 if (act) {
                   const f32x4 wv = ODD ? wv1 : wv0;
                   float gm[4 * D3];
-                  if constexpr (OFF0 > 0 && pi == 0) {   // (DMA mode: from L2, prefetched)
+                  if constexpr (OFF0 > 0 && pi == 0) {   // (two images: from L2, prefetched)
 #pragma unroll
                     for (int k = 0; k < 4; ++k) gm[k] = g0[k];
                   } else {
@@ -1838,9 +1583,9 @@ __global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_
                   pin<8>(dYa + 1);
                   if constexpr (ODD) {
                     if constexpr (STAMPED) STAMP(5);   // tensor product (+ stores)
-                    ls_prio(1);   // MFMA bursts first
+                    ls_prio<1>();   // MFMA bursts first
                     dh2_pair(dh2, dwp, dwr, pimg + LS_IW, lane);
-                    ls_prio(0);
+                    ls_prio<0>();
                     if constexpr (STAMPED) STAMP(4);   // dH2 (split + MFMA)
                   } else {
 #pragma unroll
@@ -1863,7 +1608,7 @@ __global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_
     if (act) {
       // dE/dY of edge c: sum over the 4 lane groups, then dE/du through the SH
       // polynomials (serial_code.py:50-70)
-      if constexpr (E3GNN_ROWSUM_GROUPED) {   // (the same grouped sums)
+      {   // (grouped sums, like the forward's)
         float d4a[4] = {dYa[1], dYa[2], dYa[3], dYa[4]}, d4b[4] = {dYa[5], dYa[6], dYa[7], dYa[8]};
         sum_rows4_n<4>(d4a);
         sum_rows4_n<4>(d4b);
@@ -1872,9 +1617,6 @@ __global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_
           dYa[1 + q] = d4a[q];
           dYa[5 + q] = d4b[q];
         }
-      } else {
-#pragma unroll
-        for (int q = 1; q < 9; ++q) dYa[q] = sum_rows4(dYa[q]);
       }
       if (g == 0 && er >= 0) {
         const float s3 = 1.7320508075688772f, s5 = 2.23606797749979f, c15 = s3 * s5;
@@ -1885,7 +1627,7 @@ __global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_
         const float gy = s3 * d[1] + c15 * (ux * d[4] + uz * d[6]) + 2.f * s5 * uy * d[5];
         const float gz = s3 * d[2] + c15 * (ux * d[3] + uy * d[6]) - s5 * uz * d[5] + c15 * uz * d[7];
         float* o = dgu + (int64_t)er * 3;
-        if constexpr (RPF) {
+        if constexpr (KEEP) {
           o[0] = gu_old[0] + gx;
           o[1] = gu_old[1] + gy;
           o[2] = gu_old[2] + gz;
@@ -1896,23 +1638,20 @@ __global__ __launch_bounds__(64 * BwdWpg<L>::v) __attribute__((amdgpu_waves_per_
         }
       }
       if constexpr (STAMPED) STAMP(5);
-      mlp_bwd_chain(R, emb, q0, end, lane, dh2, demb, RPF ? de_old : nullptr, KA2 ? bk : nullptr,
-                    KA2 ? a2k : nullptr, (KA2 && E3GNN_KEEP_A2 >= 2) ? a1k : nullptr);
+      mlp_bwd_chain(R, emb, q0, end, lane, dh2, demb, KEEP ? de_old : nullptr, KEEP ? bk : nullptr,
+                    KEEP ? a2k : nullptr);
     }
     if constexpr (STAMPED) STAMP(6);   // tile end: dE/dY sums, MLP chain backward
   }
   if constexpr (STAMPED) STAMP_FLUSH(blockIdx.x * WPG + wid);
-  // the last pair's DMA (pair 0 of a next tile) lands before the wave ends
-  if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 }  // namespace
 
 template <class L>
 static hipError_t bwd_ls_impl(const FusedArgs& a, hipStream_t s) {
-  constexpr int WPG = BwdWpg<L>::v;
   const int nc = a.c_end - a.c_begin;
-  hipLaunchKernelGGL(k_conv_bwd_ls<L>, dim3((nc + WPG - 1) / WPG), dim3(64 * WPG), 0, s, a.row_ptr, a.nbr,
+  hipLaunchKernelGGL(k_conv_bwd_ls<L>, dim3((nc + LS_WPG - 1) / LS_WPG), dim3(64 * LS_WPG), 0, s, a.row_ptr, a.nbr,
                      a.emb, a.Y, a.h, a.gagg, a.W, a.dxc, a.dgu, a.demb, a.c_begin, a.c_end, a.n_nodes);
   return hipGetLastError();
 }

@@ -140,20 +140,9 @@ __global__ __launch_bounds__(256) void k_gemm(GemmBatch batch) {
 //   WN = 2, NS = 1: 64 x 64 (default); WN = 1: 128 x 32 (N <= 32, the 2e
 //   block); WN = 2, NS = 2: 64 x 128 (unsplit K with N >= 128: si1 / si2^T
 //   blocks; half the tiles, A staged once per 128 columns).
-#ifndef E3GNN_NL_BK
-#define E3GNN_NL_BK 16
-#endif
-// occupancy target of k_nodelin (LDS allows 6 workgroups per CU)
-#ifndef E3GNN_NL_WAVES
-#define E3GNN_NL_WAVES 5
-#endif
-#ifndef E3GNN_NL_WIDE
-#define E3GNN_NL_WIDE 1
-#endif
-#ifndef E3GNN_NL_WIDE_KMAX
-#define E3GNN_NL_WIDE_KMAX 4096
-#endif
-constexpr int NL_BK = E3GNN_NL_BK;
+constexpr int NL_BK = 16;
+constexpr int NL_WAVES = 5;            // occupancy target of k_nodelin (LDS allows 6 workgroups per CU)
+constexpr int NL_WIDE_KMAX = 4096;     // largest K that takes the 64 x 128 tiles
 template <int WN, int NS>
 struct NlShape {
   static constexpr int BN = 32 * WN * NS, BM = 128 / WN;
@@ -164,10 +153,11 @@ constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr int NL_LDS =
     2 * cmax(NlShape<1, 1>::STAGE, cmax(NlShape<2, 1>::STAGE, NlShape<2, 2>::STAGE));
 
-// Epilogue through LDS, one 64- (or 32-) column chunk at a time: each node's
-// output is one contiguous run of CW * R floats, written as float4 (the MFMA
-// layout would scatter 4-byte stores R floats apart).  Starts with a barrier:
-// the caller's LDS readers are done.
+// Gate epilogue (epi 2 / 3) through LDS, one 64- (or 32-) column chunk at a
+// time: each node's output is one contiguous run of CW * R floats, written as
+// float4 (the MFMA layout would scatter 4-byte stores R floats apart).  The
+// general form, for the tiles the run forms below do not cover (a gate problem
+// on the wide tiles).  Starts with a barrier: the caller's LDS readers are done.
 template <int WN, int R>
 __device__ __forceinline__ void nl_epilogue(const NlProb& P, const f32x16& acc, int node0, int n0,
                                             float* lds) {
@@ -205,11 +195,6 @@ __device__ __forceinline__ void nl_epilogue(const NlProb& P, const f32x16& acc, 
     const bool full = cl[3] < ncol;
     const int64_t nrow = (int64_t)node * P.ldc;
     float* cp = P.C + nrow + P.c_off + n0 * R + j;
-    if (P.epi == 1) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (cl[q] < ncol) v[q] += cp[q];
-    }
     if (full) {
       *reinterpret_cast<float4*>(cp) = make_float4(v[0], v[1], v[2], v[3]);
     } else {
@@ -250,9 +235,6 @@ __device__ __forceinline__ void nl_epilogue(const NlProb& P, const f32x16& acc, 
 // per-element index arithmetic (the generic epilogue above spent ~0.5 VALU
 // instructions per output float on it: the si2^T launches are 1.2 GB of
 // output).  Starts with a barrier: the caller's LDS readers are done.
-#ifndef E3GNN_NL_RUNS
-#define E3GNN_NL_RUNS 1
-#endif
 // stage(lds, LDR) writes the accumulators as lds[nl * LDR + c * R + m] (the
 // tile's node nl, column c of the chunk, component m): the f32 (32x32) and
 // bf16x6 (16x16) accumulator layouts share the copy-out.
@@ -317,9 +299,6 @@ __device__ __forceinline__ void nl_epilogue_runs(const NlProb& P, const f32x16& 
 // epilogue above issued four dependent scalar global loads and four
 // activations per float4).  Gate problems split K (si2 + self-connection), so
 // only the single-block (NS = 1) tiles instantiate it.
-#ifndef E3GNN_NL_GATE_RUNS
-#define E3GNN_NL_GATE_RUNS 1
-#endif
 template <int BM, int CW, int R, int LDSF, class Stage>
 __device__ __forceinline__ void nl_epi_gate(const NlProb& P, int node0, int n0, float* lds, Stage stage) {
   constexpr int T = BM / R;
@@ -385,15 +364,11 @@ __device__ __forceinline__ void nl_epilogue_gate(const NlProb& P, const f32x16& 
 
 // Operand loads through buffer descriptors based at the tile (a 32-bit lane
 // offset fixed over the k loop, the k-step's advance a scalar offset: no
-// 64-bit addresses to keep live).  Optionally (E3GNN_NL_DEPTH2, 64 x 64 tiles
-// only: the wider tiles' second slot does not fit five waves per SIMD) two
-// register slots keep the loads of k-step kt + 2 in flight while step kt
-// computes.  Rows past the problem's nodes read 0 (outside the descriptor).
-// (a second register slot for the 64 x 64 tiles measured 0.17 ms per step
-// SLOWER: 5.36 vs 5.19 ms of node linears, same box; kept as an option)
-#ifndef E3GNN_NL_DEPTH2
-#define E3GNN_NL_DEPTH2 0
-#endif
+// 64-bit addresses to keep live).  One register slot: step kt + 1's loads are
+// in flight while step kt computes.  Rows past the problem's nodes read 0
+// (outside the descriptor).  (A second register slot for the 64 x 64 tiles
+// measured 0.17 ms per step SLOWER: 5.36 vs 5.19 ms of node linears, same box;
+// the wider tiles' second slot does not fit five waves per SIMD.)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t nl_rsrc(const float* p, int64_t nbytes) {
   const int n = nbytes <= 0 ? 0 : (nbytes > 0x7fffffff ? 0x7fffffff : (int)nbytes);
@@ -442,10 +417,7 @@ __device__ __forceinline__ void nl_tile(const NlProb& P, int local, float* lds) 
     const int k = u / (BN / 4), c = 4 * (u - k * (BN / 4));
     b_v[i] = (UB % 256 == 0 || u < UB) ? (k * P.N + c) * 4 : 0x7ffffff0;
   }
-  // two register slots where the registers allow it (64 x 64 tiles: one
-  // float4 of A and one of B per thread and slot); one otherwise
-  constexpr int DEPTH = (E3GNN_NL_DEPTH2 && WN == 2 && NS == 1) ? 2 : 1;
-  float4 ra[DEPTH][NA], rb[DEPTH][NB];
+  float4 ra[NA], rb[NB];   // the register slot
   auto load = [&](int k0, float4(&xa)[NA], float4(&xb)[NB]) __attribute__((always_inline)) {
     const bool second = k0 >= P.K1;
     const int kk0 = second ? k0 - P.K1 : k0;
@@ -498,8 +470,7 @@ __device__ __forceinline__ void nl_tile(const NlProb& P, int local, float* lds) 
 
   const int nk = (P.K + BK - 1) / BK;
   const int nk1 = (NS == 1 && P.K > P.K1) ? P.K1 / BK : nk;
-  // step kt (DEPTH 2): LDS stage kt & 1 holds kt; register slot (kt + 1) & 1
-  // holds step kt + 1 and slot kt & 1 step kt + 2 (both in flight).
+  // LDS stage kt & 1 holds step kt.
   // wave (wr, wc), sub-tile s: columns s * 32 * WN + wc * 32 + (0..31), so
   // chunk s of the epilogue is one contiguous 32 * WN column range
   auto compute = [&](int buf, f32x16(&c)[NS]) __attribute__((always_inline)) {
@@ -516,21 +487,10 @@ __device__ __forceinline__ void nl_tile(const NlProb& P, int local, float* lds) 
     }
   };
   auto step = [&](int kt, f32x16(&c)[NS]) __attribute__((always_inline)) {
-    if constexpr (DEPTH == 2) {
-      if (kt & 1) {
-        compute(1, c);
-        if (kt + 1 < nk) store(0, ra[0], rb[0]);
-        if (kt + 3 < nk) load((kt + 3) * BK, ra[0], rb[0]);
-      } else {
-        compute(0, c);
-        if (kt + 1 < nk) store(1, ra[DEPTH - 1], rb[DEPTH - 1]);
-        if (kt + 3 < nk) load((kt + 3) * BK, ra[DEPTH - 1], rb[DEPTH - 1]);
-      }
-    } else {  // one slot: step kt + 1's loads cover step kt's MFMA work
-      if (kt + 1 < nk) load((kt + 1) * BK, ra[0], rb[0]);
-      compute(kt & 1, c);
-      if (kt + 1 < nk) store((kt + 1) & 1, ra[0], rb[0]);
-    }
+    // step kt + 1's loads cover step kt's MFMA work
+    if (kt + 1 < nk) load((kt + 1) * BK, ra, rb);
+    compute(kt & 1, c);
+    if (kt + 1 < nk) store((kt + 1) & 1, ra, rb);
     __syncthreads();
   };
   f32x16 acc[NS];
@@ -538,12 +498,8 @@ __device__ __forceinline__ void nl_tile(const NlProb& P, int local, float* lds) 
   for (int sub = 0; sub < NS; ++sub)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[sub][i] = 0.f;
-  load(0, ra[0], rb[0]);
-  store(0, ra[0], rb[0]);
-  if constexpr (DEPTH == 2) {
-    if (nk > 1) load(BK, ra[DEPTH - 1], rb[DEPTH - 1]);
-    if (nk > 2) load(2 * BK, ra[0], rb[0]);
-  }
+  load(0, ra, rb);
+  store(0, ra, rb);
   __syncthreads();
 #pragma unroll 1
   for (int kt = 0; kt < nk1; ++kt) step(kt, acc);
@@ -565,16 +521,16 @@ __device__ __forceinline__ void nl_tile(const NlProb& P, int local, float* lds) 
   }
 #pragma unroll
   for (int sub = 0; sub < NS; ++sub) {
-    if (E3GNN_NL_RUNS && P.epi <= 1)
+    if (P.epi <= 1)
       nl_epilogue_runs<WN, R>(P, acc[sub], node0, n0 + sub * 32 * WN, lds);
-    else if (E3GNN_NL_GATE_RUNS && NS == 1 && P.epi >= 2 && (R > 1) == (P.epi == 3))
+    else if (NS == 1 && (R > 1) == (P.epi == 3))
       nl_epilogue_gate<WN, R>(P, acc[sub], node0, n0 + sub * 32 * WN, lds);
     else
       nl_epilogue<WN, R>(P, acc[sub], node0, n0 + sub * 32 * WN, lds);
   }
 }
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E3GNN_NL_WAVES, 8))) void
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NL_WAVES, 8))) void
 k_nodelin(NlBatch batch) {
   __shared__ __attribute__((aligned(16))) float lds[NL_LDS];
   const int tile = blockIdx.x;
@@ -988,10 +944,8 @@ k_nodelin_s(NlBatch batch) {
   }
 }
 
-#ifndef E3GNN_NLB_WAVES
-#define E3GNN_NLB_WAVES 3
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(E3GNN_NLB_WAVES, 8))) void
+constexpr int NLB_WAVES = 3;
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NLB_WAVES, 8))) void
 k_nodelin_b(NlBatch batch) {
   __shared__ __attribute__((aligned(16))) float lds[NB_LDSF];
   const int tile = blockIdx.x;
@@ -1078,7 +1032,7 @@ bool add_nl(NlBatch& b, const NlProb& p) {
     if (p.K > p.K1 && (!al(p.A2) || p.lda2 % 4 || p.a_off2 % 4 || p.K1 % NL_BK)) return false;
     q.kind = 0;
     q.wn = p.N <= 32 ? 1 : 2;
-    q.ns = (E3GNN_NL_WIDE && q.wn == 2 && p.K == p.K1 && p.K <= E3GNN_NL_WIDE_KMAX && p.N >= 128) ? 2 : 1;
+    q.ns = (q.wn == 2 && p.K == p.K1 && p.K <= NL_WIDE_KMAX && p.N >= 128) ? 2 : 1;
     const int BM = 128 / q.wn, BN = 32 * q.wn * q.ns;
     q.tpn = BM / p.R;
     tm = (p.nodes + q.tpn - 1) / q.tpn;

@@ -735,33 +735,22 @@ __global__ void k_gather_rows(int j_begin, int n, int D, const int* __restrict__
 // that of k_gather_rows.  (Measured against two columns per lane with 8 rows
 // in flight -- 85 VGPRs, 5 waves per SIMD: 1.39 vs 0.94 ms per 480-wide
 // launch; the occupancy of this 20-register form hides the row latency better;
-// rows in flight U = 2 / 4 / 8 and non-temporal loads measured the same.)
-#ifndef E3GNN_GATHER_V2
-#define E3GNN_GATHER_V2 0
-#endif
-// rows of 65..128 float4 (SevenNet-0's middle blocks: 120): both halves of a
-// row per pass, 8 rows in flight (E3GNN_GATHER_2H: 3.22 -> 3.13-3.15 ms for
-// the three launches of a step, same box; profiles/r06_s14_*)
-#ifndef E3GNN_GATHER_2H
-#define E3GNN_GATHER_2H 1
-#endif
-#ifndef E3GNN_GATHER_U2
-#define E3GNN_GATHER_U2 8
-#endif
-#ifndef E3GNN_GATHER_U
-#define E3GNN_GATHER_U 4
-#endif
+// rows in flight U = 2 / 4 / 8 and non-temporal loads measured the same; row
+// ids read once per 64 and broadcast by v_readlane were tried and rejected.)
+// Rows of 65..128 float4 (SevenNet-0's middle blocks: 120): both halves of a
+// row per pass, 8 rows in flight (3.22 -> 3.13-3.15 ms for the three launches
+// of a step, same box; profiles/r06_s14_*).
 // blockIdx.y = 1: the second (src, dst) pair of launch_gather_rows2
 __global__ void k_gather_rows4(int j_begin, int n, int D4, const int* __restrict__ ptr,
                                const int* __restrict__ perm, const float4* __restrict__ src,
                                float4* __restrict__ dst, int acc, const float4* __restrict__ src2,
                                float4* __restrict__ dst2) {
-  constexpr int U = E3GNN_GATHER_U;
+  constexpr int U = 4, U2 = 8;   // rows in flight with one column per lane, with two
   if (blockIdx.y) {
     src = src2;
     dst = dst2;
   }
-  const int j = j_begin + xcd_block() * 4 + (threadIdx.x >> 6);
+  const int j = j_begin + blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (j >= n) return;
   const int b = ptr[j], en = ptr[j + 1];
@@ -771,38 +760,9 @@ __global__ void k_gather_rows4(int j_begin, int n, int D4, const int* __restrict
     s.z += v.z;
     s.w += v.w;
   };
-#if E3GNN_GATHER_V2
-  // the node's row ids once per 64 (lane i holds perm[b + i]), each row id
-  // broadcast from its lane (v_readlane: a scalar, no dependent index load
-  // per batch of rows), the same ascending order as below
-  if (en - b <= 64) {
-    const int myidx = b + lane < en ? perm[b + lane] : 0;
-    const int cnt = en - b;
-    for (int c = lane; c < D4; c += 64) {
-      float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-      int k = 0;
-      for (; k + U <= cnt; k += U) {
-        float4 v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int row = __builtin_amdgcn_readlane(myidx, k + u);
-          v[u] = src[(int64_t)row * D4 + c];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) add(s, v[u]);
-      }
-      for (; k < cnt; ++k) add(s, src[(int64_t)__builtin_amdgcn_readlane(myidx, k) * D4 + c]);
-      if (acc) add(s, dst[(int64_t)j * D4 + c]);
-      dst[(int64_t)j * D4 + c] = s;
-    }
-    return;
-  }
-#endif
-#if E3GNN_GATHER_2H
   // rows of 65..128 float4: both halves of each row in the same pass (twice
   // the loads in flight per lane, one pass over the row indices)
   if (D4 > 64 && D4 <= 128) {
-    constexpr int U2 = E3GNN_GATHER_U2;
     const int c0 = lane, c1 = lane + 64;
     const bool h1 = c1 < D4;
     float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
@@ -834,7 +794,6 @@ __global__ void k_gather_rows4(int j_begin, int n, int D4, const int* __restrict
     if (h1) dst[(int64_t)j * D4 + c1] = s1;
     return;
   }
-#endif
   for (int c = lane; c < D4; c += 64) {
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     int q = b;

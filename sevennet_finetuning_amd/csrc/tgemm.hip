@@ -34,15 +34,7 @@ namespace {
 
 // tile shapes: MODE 0 = 64x64x16 (waves 2 x 2 over the tile), MODE 1 =
 // 32x32xTG_M1_BK (waves over k); NS = register ring depth in k steps
-#ifndef TG_M1_BK
-#define TG_M1_BK 32
-#endif
-#ifndef TG_NS0
-#define TG_NS0 4
-#endif
-#ifndef TG_NS1
-#define TG_NS1 4
-#endif
+constexpr int TG_M1_BK = 32, TG_NS0 = 4, TG_NS1 = 4;
 template <int MODE> struct TgShape {
   static constexpr int BM = MODE ? 32 : 64;         // tile rows = columns
   static constexpr int BK = MODE ? TG_M1_BK : 16;   // k per step

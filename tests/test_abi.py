@@ -2,6 +2,9 @@
 (no compute calls: this runs without a GPU)."""
 import ctypes
 import subprocess
+import sys
+
+import pytest
 
 from sevennet_finetuning_amd import _lib
 
@@ -17,6 +20,22 @@ def test_library_exports_header_symbols():
                          text=True).stdout
     exported = {line.split()[-1] for line in out.splitlines() if ' T ' in line}
     assert set(declared) <= exported
+
+
+def test_build_lib_refuses_variants_as_the_product(tmp_path):
+    """defines without a path of their own would rebuild the product library as
+    a variant, and an unknown switch name would build the default kernels under
+    a variant's name: both are refused before anything is compiled"""
+    from sevennet_finetuning_amd import build_lib
+    with pytest.raises(ValueError, match='out'):
+        build_lib.build(defines=['E3GNN_DH2_X3=0'])
+    with pytest.raises(ValueError, match='E3GNN_LS_DMA.*E3GNN_STAMPS_FWD'):
+        build_lib.build(out=str(tmp_path / 'v.so'), defines=['E3GNN_DH2_X3=0', 'E3GNN_LS_DMA=1'])
+    assert not (tmp_path / 'v.so').exists()
+    # the command line goes through the same check
+    r = subprocess.run([sys.executable, '-m', 'sevennet_finetuning_amd.build_lib', '-DE3GNN_STAMPS'],
+                       capture_output=True, text=True)
+    assert r.returncode != 0 and '--out' in r.stderr
 
 
 def test_abi_version_and_errors():
