@@ -486,7 +486,7 @@ int e3gnn_d3_compute(e3gnn_d3* h, int64_t n, const double* pos, const double* ce
 /* ---- diagnostics ---- */
 /* Kernel implementation of the convolution: 0 = fused radial-MLP + tensor
  * product (default), 1 = unfused v1 kernels (per-edge weights materialised in
- * HBM; kept as an independent cross-check).  Env E3GNN_IMPL=v1 sets 1.
+ * HBM; kept as an independent cross-check).  This call is the only selector.
  * Takes effect at the next e3gnn_graph_set / e3gnn_energy_forces. */
 int e3gnn_set_impl(e3gnn_ctx* c, int impl);
 /* enable per-kernel-class HIP-event timing on the context */

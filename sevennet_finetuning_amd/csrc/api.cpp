@@ -249,11 +249,9 @@ struct e3gnn_ctx {
     return (v && std::string(v) == "0") ? 0 : 1;
   }();
   // 0: fused radial-MLP + TP kernels (fused.hip); 1: the unfused v1 kernels
-  // (materialised per-edge weights; kept as an independent cross-check)
-  int impl = [] {
-    const char* v = std::getenv("E3GNN_IMPL");
-    return (v && std::string(v) == "v1") ? 1 : 0;
-  }();
+  // (materialised per-edge weights; kept as an independent cross-check,
+  // e3gnn_set_impl)
+  int impl = 0;
   int graph_impl = 0;  // impl in force since the last e3gnn_graph_set (buffers sized for it)
   // per layer
   std::vector<DBuf> x, grad, h, y, w, a1, a2;
@@ -1359,84 +1357,13 @@ int e3gnn_graph_set(e3gnn_ctx* c, int64_t n_local, int64_t n_ghost, int64_t n_ed
   return E3GNN_OK;
 }
 
-// Parts of one interaction block for the halo overlap (e3gnn.h):
-// part 0 needs only the owned rows of the block's input features (it runs
-// while the ghost rows are in flight): self_interaction_1 of the owned rows and
-// the convolution of the interior centres [0, n_int); part 1: the ghost rows'
-// self_interaction_1, the boundary centres [n_int, n_local), si2 +
-// self-connection + gate.  The v1 kernels run whole in part 1.
-int e3gnn_layer_forward_part(e3gnn_ctx* c, int t, int part, void* stream) {
-  if (!c) return fail(E3GNN_ERR_ARG, "null context");
+// The convolution of the v1 cross-check (impl 1), over all edges: the radial
+// MLP materialises the per-edge weights w, the tensor-product kernels read them.
+static int v1_conv_forward(e3gnn_ctx* c, int t, hipStream_t s) {
   e3gnn_model* m = c->m;
-  if (t < 0 || t >= m->nlayer) return fail(E3GNN_ERR_ARG, "layer out of range");
-  if (part != 0 && part != 1) return fail(E3GNN_ERR_ARG, "part must be 0 or 1");
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = (hipStream_t)stream;
-  // generic engine: the whole layer after the halo of x[t] (part 1)
-  if (c->gen) {
-    if (part == 1) HIPCHK(gen_layer_forward(c->gen, m->gen, gen_graph(c), t, s));
-    return E3GNN_OK;
-  }
-  const int64_t n = c->n, nl = c->nl, E = c->E;
-  const int dx = irreps_dim(m->irreps[t]), dg = irreps_dim(m->gin[t]);
-  const int dm = irreps_dim(m->mid[t]), W = m->W[t];
-  const bool last = t == m->nlayer - 1;
-  const int kind = t == 0 ? 0 : (last ? 2 : 1);   // block kind (timing class, v1 kernels)
-  const int code = m->kcode(t);                    // fused kernel kind code
-  const bool fused = c->graph_impl == 0;
-  const int64_t n_int = fused ? c->n_int : 0;
-  auto conv_fwd = [&](int64_t c0, int64_t c1, double e_share) -> int {
-    if (c1 <= c0) return E3GNN_OK;
-    Region r(c, s, C_CONV_FWD + kind,
-             e_share * (tp_flops_per_edge(code) + 2.0 * (8 * 64 + 64 * 64 + 64 * W)),
-             e_share * 4 * (8 + 9 + 2 + dx) + (c1 - c0) * 4.0 * dm);
-    FusedArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.row_ptr = c->row_ptr.i();
-    a.nbr = c->nbr.i();
-    a.emb = c->emb.f();
-    a.Y = c->Y.f();
-    a.h = c->h[t].f();
-    a.agg = c->agg.f();
-    a.W = mlp_ptrs(m, t);
-    a.n_centers = (int)nl;
-    a.n_nodes = (int)n;
-    a.denom = m->denom[t];
-    a.c_begin = (int)c0;
-    a.c_end = (int)c1;
-    HIPCHK(launch_conv_fwd(code, a, s));
-    return E3GNN_OK;
-  };
-  if (part == 0) {
-    if (!fused) return E3GNN_OK;
-    {
-      Region r(c, s, C_LINEAR, lin_flops(*m->si1[t], nl));
-      NlBatch nb;
-      if (c->nodelin && nl_batch(nb, *m->nl_si1[t], c->x[t].f(), dx, nullptr, 0, c->h[t].f(), dx, nl, 0))
-        HIPCHK(launch_nodelin(nb, s));
-      else
-        HIPCHK(launch_gemm(lin_fwd(*m->si1[t], c->x[t].f(), dx, c->h[t].f(), dx, nl, 0), s));
-    }
-    return conv_fwd(0, n_int, (double)c->e_int);
-  }
-  // ---- part 1
-  {
-    const int64_t r0 = fused ? nl : 0;  // rows not done in part 0
-    Region r(c, s, C_LINEAR, lin_flops(*m->si1[t], n - r0));
-    NlBatch nb;
-    if (n > r0 && c->nodelin &&
-        nl_batch(nb, *m->nl_si1[t], c->x[t].f() + r0 * dx, dx, nullptr, 0, c->h[t].f() + r0 * dx, dx,
-                 n - r0, 0))
-      HIPCHK(launch_nodelin(nb, s));
-    else if (n > r0)
-      HIPCHK(launch_gemm(lin_fwd(*m->si1[t], c->x[t].f() + r0 * dx, dx, c->h[t].f() + r0 * dx, dx,
-                                 n - r0, 0), s));
-  }
-  if (fused) {
-    // fused radial MLP + tensor product + segmented sum (fused.hip)
-    const int rc = conv_fwd(n_int, nl, (double)(E - c->e_int));
-    if (rc) return rc;
-  } else {
+  const int64_t nl = c->nl, E = c->E;
+  const int dx = irreps_dim(m->irreps[t]), dm = irreps_dim(m->mid[t]), W = m->W[t];
+  const int kind = t == 0 ? 0 : (t == m->nlayer - 1 ? 2 : 1);
   // radial MLP: emb -> 64 -> 64 -> W  (convolution.py:97-106)
   {
     Region r(c, s, C_MLP_FWD, 2.0 * E * (8 * 64 + 64 * 64 + 64 * W),
@@ -1464,7 +1391,7 @@ int e3gnn_layer_forward_part(e3gnn_ctx* c, int t, int part, void* stream) {
   }
   // tensor product + segmented neighbour sum
   {
-    Region r(c, s, C_TP_FWD, tp_flops_per_edge(code) * E,
+    Region r(c, s, C_TP_FWD, tp_flops_per_edge(m->kcode(t)) * E,
              (double)E * 4 * (W + 9 + dx + 2) + nl * 4.0 * dm);
     TpArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1478,6 +1405,80 @@ int e3gnn_layer_forward_part(e3gnn_ctx* c, int t, int part, void* stream) {
     a.denom = m->denom[t];
     HIPCHK(launch_tp_fwd(kind, a, s));
   }
+  return E3GNN_OK;
+}
+
+// Parts of one interaction block for the halo overlap (e3gnn.h):
+// part 0 needs only the owned rows of the block's input features (it runs
+// while the ghost rows are in flight): self_interaction_1 of the owned rows and
+// the convolution of the interior centres [0, n_int); part 1: the ghost rows'
+// self_interaction_1, the boundary centres [n_int, n_local), si2 +
+// self-connection + gate.  The v1 kernels run whole in part 1.
+int e3gnn_layer_forward_part(e3gnn_ctx* c, int t, int part, void* stream) {
+  if (!c) return fail(E3GNN_ERR_ARG, "null context");
+  e3gnn_model* m = c->m;
+  if (t < 0 || t >= m->nlayer) return fail(E3GNN_ERR_ARG, "layer out of range");
+  if (part != 0 && part != 1) return fail(E3GNN_ERR_ARG, "part must be 0 or 1");
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  // generic engine: the whole layer after the halo of x[t] (part 1)
+  if (c->gen) {
+    if (part == 1) HIPCHK(gen_layer_forward(c->gen, m->gen, gen_graph(c), t, s));
+    return E3GNN_OK;
+  }
+  const int64_t n = c->n, nl = c->nl, E = c->E, n_int = c->n_int;
+  const int dx = irreps_dim(m->irreps[t]), dg = irreps_dim(m->gin[t]);
+  const int dm = irreps_dim(m->mid[t]), W = m->W[t];
+  const bool last = t == m->nlayer - 1;
+  const int kind = t == 0 ? 0 : (last ? 2 : 1);   // block kind (timing class)
+  const int code = m->kcode(t);                    // fused kernel kind code
+  // self_interaction_1 of the rows [r0, r1)
+  auto si1 = [&](int64_t r0, int64_t r1) -> int {
+    Region r(c, s, C_LINEAR, lin_flops(*m->si1[t], r1 - r0));
+    if (r1 <= r0) return E3GNN_OK;
+    const float* x = c->x[t].f() + r0 * dx;
+    float* h = c->h[t].f() + r0 * dx;
+    NlBatch nb;
+    if (c->nodelin && nl_batch(nb, *m->nl_si1[t], x, dx, nullptr, 0, h, dx, r1 - r0, 0))
+      HIPCHK(launch_nodelin(nb, s));
+    else
+      HIPCHK(launch_gemm(lin_fwd(*m->si1[t], x, dx, h, dx, r1 - r0, 0), s));
+    return E3GNN_OK;
+  };
+  // fused radial MLP + tensor product + segmented sum (fused.hip) of the
+  // centres [c0, c1)
+  auto conv_fwd = [&](int64_t c0, int64_t c1, double e_share) -> int {
+    if (c1 <= c0) return E3GNN_OK;
+    Region r(c, s, C_CONV_FWD + kind,
+             e_share * (tp_flops_per_edge(code) + 2.0 * (8 * 64 + 64 * 64 + 64 * W)),
+             e_share * 4 * (8 + 9 + 2 + dx) + (c1 - c0) * 4.0 * dm);
+    FusedArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.row_ptr = c->row_ptr.i();
+    a.nbr = c->nbr.i();
+    a.emb = c->emb.f();
+    a.Y = c->Y.f();
+    a.h = c->h[t].f();
+    a.agg = c->agg.f();
+    a.W = mlp_ptrs(m, t);
+    a.n_centers = (int)nl;
+    a.n_nodes = (int)n;
+    a.denom = m->denom[t];
+    a.c_begin = (int)c0;
+    a.c_end = (int)c1;
+    HIPCHK(launch_conv_fwd(code, a, s));
+    return E3GNN_OK;
+  };
+  if (c->graph_impl == 1) {  // the v1 cross-check: all rows and edges, in part 1
+    if (part == 0) return E3GNN_OK;
+    if (const int rc = si1(0, n)) return rc;
+    if (const int rc = v1_conv_forward(c, t, s)) return rc;
+  } else if (part == 0) {
+    if (const int rc = si1(0, nl)) return rc;
+    return conv_fwd(0, n_int, (double)c->e_int);
+  } else {
+    if (const int rc = si1(nl, n)) return rc;
+    if (const int rc = conv_fwd(n_int, nl, (double)(E - c->e_int))) return rc;
   }
   // self_interaction_2 + self_connection (intro/outro) + gate: on k_nodelin
   // one K-concatenated problem per output block, the 0e block first (its
@@ -1560,96 +1561,16 @@ int e3gnn_readout(e3gnn_ctx* c, float* energy, float* atomic_energy, void* strea
   return E3GNN_OK;
 }
 
-// Parts of a block's backward for the halo overlap (e3gnn.h): part 0 makes
-// everything the GHOST rows of dE/dx need (gate + si2 backward of the owned
-// rows, the boundary centres' edges, the ghost rows' gather and
-// self_interaction_1 backward), so the reverse exchange can start; part 1 does
-// the interior centres and the owned rows.  The v1 kernels run whole in part 0.
-int e3gnn_layer_backward_part(e3gnn_ctx* c, int t, int part, void* stream) {
-  if (!c) return fail(E3GNN_ERR_ARG, "null context");
+// The convolution backward of the v1 cross-check (impl 1), over all edges:
+// the tensor-product backward writes dE/dw per edge, the radial MLP's backward
+// reads it.
+static int v1_conv_backward(e3gnn_ctx* c, int t, hipStream_t s) {
   e3gnn_model* m = c->m;
-  if (t < 0 || t >= m->nlayer) return fail(E3GNN_ERR_ARG, "layer out of range");
-  if (part != 0 && part != 1) return fail(E3GNN_ERR_ARG, "part must be 0 or 1");
-  if (!c->readout_done) return fail(E3GNN_ERR_ARG, "e3gnn_readout must precede the backward");
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = (hipStream_t)stream;
-  // generic engine: the whole layer before the reverse halo of dE/dx[t] (part 0)
-  if (c->gen) {
-    if (part == 0) HIPCHK(gen_layer_backward(c->gen, m->gen, gen_graph(c), t, s));
-    return E3GNN_OK;
-  }
-  const int64_t n = c->n, nl = c->nl, E = c->E;
-  const int dx = irreps_dim(m->irreps[t]), dg = irreps_dim(m->gin[t]);
-  const int dm = irreps_dim(m->mid[t]), W = m->W[t];
-  const bool last = t == m->nlayer - 1;
-  const int kind = t == 0 ? 0 : (last ? 2 : 1);   // block kind (timing class, v1 kernels)
-  const int code = m->kcode(t);                    // fused kernel kind code
-  const bool fused = c->graph_impl == 0;
-  if (!fused && part == 1) return E3GNN_OK;
-  const int64_t n_int = c->n_int, e_int = c->e_int;
-  if (part == 0) {
-    {
-      Region r(c, s, C_GATE_BWD, 0, nl * 4.0 * (2 * dg + irreps_dim(m->irreps[t + 1])));
-      HIPCHK(launch_gate_bwd((int)nl, last, m->gdims[t], c->y[t].f(), c->grad[t + 1].f(), c->dy.f(), s));
-    }
-    {
-      Region r(c, s, C_LINEAR, lin_flops(*m->si2[t], nl));
-      NlBatch nb;
-      if (c->nodelin && nl_batch(nb, *m->nl_si2t[t], c->dy.f(), dg, nullptr, 0, c->agg.f(), dm, nl, 0))
-        HIPCHK(launch_nodelin(nb, s));
-      else
-        HIPCHK(launch_gemm(lin_bwd(*m->si2[t], c->dy.f(), dg, c->agg.f(), dm, nl, 0), s));
-    }
-  }
-  // first / middle blocks: per-edge dE/dx (dxc) + transposed-CSR gather; the
-  // last block (224 message channels) writes dE/dx per neighbour node
-  const bool gather = !fused || !last;
-  if (fused) {
-    FusedArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.row_ptr = c->row_ptr.i();
-    a.nbr = c->nbr.i();
-    a.emb = c->emb.f();
-    a.Y = c->Y.f();
-    a.h = c->h[t].f();
-    a.gagg = c->agg.f();
-    a.center = c->center.i();
-    a.n_edges = (int)E;
-    a.src_ptr = c->src_ptr.i();
-    a.src_perm = c->src_perm.i();
-    a.dh = c->dh.f();  // the last block writes its dE/dx rows here
-    a.dxc = (!last && t > 0) ? c->dxc.f() : nullptr;
-    a.dgu = c->dgu.f();
-    a.demb = c->demb.f();
-    a.W = mlp_ptrs(m, t);
-    a.n_centers = (int)nl;
-    a.n_nodes = (int)n;
-    // part 0: boundary centres / their edges / ghost neighbour nodes
-    a.c_begin = (int)(part == 0 ? n_int : 0);
-    a.c_end = (int)(part == 0 ? nl : n_int);
-    a.node_begin = (int)(part == 0 ? nl : 0);
-    a.node_end = (int)(part == 0 ? n : nl);
-    double ef = (double)(part == 0 ? E - e_int : e_int);
-    if (last && c->timing && a.node_end > a.node_begin) {
-      // the last block's launch covers the edges of its neighbour-node range
-      int32_t q[2];
-      HIPCHK(hipMemcpyAsync(&q[0], a.src_ptr + a.node_begin, 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(&q[1], a.src_ptr + a.node_end, 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      ef = (double)(q[1] - q[0]);
-    }
-    // empty ranges launch nothing (and are not counted as launches)
-    if (last ? a.node_end > a.node_begin : a.c_end > a.c_begin) {
-      // algorithmic FLOP (the forward radial MLP the kernel recomputes is not
-      // counted): dE/dx + dE/dY = 2 x TP; dE/dw = TP, dH2 = dw W2^T, MLP chain
-      const double xf = 3.0 * tp_flops_per_edge(code) + 2.0 * (64 * W + 64 * 64 + 8 * 64);
-      Region r(c, s, C_CONV_BWD_X + kind, xf * ef,
-               ef * 4 * (8 + 9 + 2 + 3 + 8) + (a.c_end - a.c_begin) * 4.0 * dm);
-      HIPCHK(last ? launch_conv_bwd_nbr_last(code, a, s) : launch_conv_bwd_ls(code, a, s));
-    }
-  } else {
+  const int64_t nl = c->nl, E = c->E;
+  const int dx = irreps_dim(m->irreps[t]), dm = irreps_dim(m->mid[t]), W = m->W[t];
+  const int kind = t == 0 ? 0 : (t == m->nlayer - 1 ? 2 : 1);
   {
-    Region r(c, s, C_TP_BWD, 3.0 * tp_flops_per_edge(code) * E,
+    Region r(c, s, C_TP_BWD, 3.0 * tp_flops_per_edge(m->kcode(t)) * E,
              (double)E * 4 * (2 * W + 2 * 9 + dx + (t > 0 ? dx : 0) + 2) + nl * 4.0 * dm);
     TpArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1689,18 +1610,59 @@ int e3gnn_layer_backward_part(e3gnn_ctx* c, int t, int part, void* stream) {
     add_prob(b, p);
     HIPCHK(launch_gemm(b, s));
   }
+  return E3GNN_OK;
+}
+
+// Parts of a block's backward for the halo overlap (e3gnn.h): part 0 makes
+// everything the GHOST rows of dE/dx need (gate + si2 backward of the owned
+// rows, the boundary centres' edges, the ghost rows' gather and
+// self_interaction_1 backward), so the reverse exchange can start; part 1 does
+// the interior centres and the owned rows.  The v1 kernels run whole in part 0.
+int e3gnn_layer_backward_part(e3gnn_ctx* c, int t, int part, void* stream) {
+  if (!c) return fail(E3GNN_ERR_ARG, "null context");
+  e3gnn_model* m = c->m;
+  if (t < 0 || t >= m->nlayer) return fail(E3GNN_ERR_ARG, "layer out of range");
+  if (part != 0 && part != 1) return fail(E3GNN_ERR_ARG, "part must be 0 or 1");
+  if (!c->readout_done) return fail(E3GNN_ERR_ARG, "e3gnn_readout must precede the backward");
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  // generic engine: the whole layer before the reverse halo of dE/dx[t] (part 0)
+  if (c->gen) {
+    if (part == 0) HIPCHK(gen_layer_backward(c->gen, m->gen, gen_graph(c), t, s));
+    return E3GNN_OK;
   }
-  if (t > 0) {
-    // rows of this part: ghosts [nl, n) in part 0, owned [0, nl) in part 1
-    // (the v1 kernels: all rows, in part 0)
-    const int64_t r0 = !fused ? 0 : (part == 0 ? nl : 0), r1 = !fused ? n : (part == 0 ? n : nl);
+  const int64_t n = c->n, nl = c->nl, E = c->E;
+  const int dx = irreps_dim(m->irreps[t]), dg = irreps_dim(m->gin[t]);
+  const int dm = irreps_dim(m->mid[t]), W = m->W[t];
+  const bool last = t == m->nlayer - 1;
+  const int kind = t == 0 ? 0 : (last ? 2 : 1);   // block kind (timing class)
+  const int code = m->kcode(t);                    // fused kernel kind code
+  const int64_t n_int = c->n_int, e_int = c->e_int;
+  // gate + self_interaction_2 backward of the owned rows
+  auto out_bwd = [&]() -> int {
+    {
+      Region r(c, s, C_GATE_BWD, 0, nl * 4.0 * (2 * dg + irreps_dim(m->irreps[t + 1])));
+      HIPCHK(launch_gate_bwd((int)nl, last, m->gdims[t], c->y[t].f(), c->grad[t + 1].f(), c->dy.f(), s));
+    }
+    Region r(c, s, C_LINEAR, lin_flops(*m->si2[t], nl));
+    NlBatch nb;
+    if (c->nodelin && nl_batch(nb, *m->nl_si2t[t], c->dy.f(), dg, nullptr, 0, c->agg.f(), dm, nl, 0))
+      HIPCHK(launch_nodelin(nb, s));
+    else
+      HIPCHK(launch_gemm(lin_bwd(*m->si2[t], c->dy.f(), dg, c->agg.f(), dm, nl, 0), s));
+    return E3GNN_OK;
+  };
+  // dE/dx of the block's input rows [r0, r1): the transposed-CSR gather of the
+  // per-edge dE/dx (dxc) where the convolution wrote that, self_interaction_1
+  // backward, and with the owned rows [0, nl) the self-connection's backward
+  auto in_bwd = [&](int64_t r0, int64_t r1, bool gather, bool owned) -> int {
+    if (t == 0) return E3GNN_OK;
     if (gather && r1 > r0) {
       Region r(c, s, C_GATHER, 0, (double)E * 4 * (dx + 1) * (r1 - r0) / std::max<int64_t>(n, 1) +
                                       (r1 - r0) * 4.0 * dx);
       HIPCHK(launch_gather_rows_range((int)r0, (int)r1, dx, c->src_ptr.i(), c->src_perm.i(),
                                       c->dxc.f(), c->dh.f(), s));
     }
-    const bool owned = !fused || part == 1;
     Region r(c, s, C_LINEAR, lin_flops(*m->si1[t], r1 - r0) + (owned ? lin_flops(*m->sc[t], nl) : 0));
     // k_nodelin: owned rows [0, nl) as one si1^T + sc^T problem per block,
     // the remaining rows (ghosts) si1^T alone
@@ -1718,8 +1680,64 @@ int e3gnn_layer_backward_part(e3gnn_ctx* c, int t, int part, void* stream) {
                                    r1 - r0, 0), s));
       if (owned) HIPCHK(launch_gemm(lin_bwd(*m->sc[t], c->dy.f(), dg, c->grad[t].f(), dx, nl, 1), s));
     }
+    return E3GNN_OK;
+  };
+  if (c->graph_impl == 1) {  // the v1 cross-check: all rows and edges, in part 0
+    if (part == 1) return E3GNN_OK;
+    if (const int rc = out_bwd()) return rc;
+    if (const int rc = v1_conv_backward(c, t, s)) return rc;
+    return in_bwd(0, n, true, true);
   }
-  return E3GNN_OK;
+  if (part == 0) {
+    if (const int rc = out_bwd()) return rc;
+  }
+  // fused radial-MLP + tensor-product backward (fused.hip).  First / middle
+  // blocks: per-edge dE/dx (dxc) + transposed-CSR gather; the last block (224
+  // message channels) writes dE/dx per neighbour node
+  FusedArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.row_ptr = c->row_ptr.i();
+  a.nbr = c->nbr.i();
+  a.emb = c->emb.f();
+  a.Y = c->Y.f();
+  a.h = c->h[t].f();
+  a.gagg = c->agg.f();
+  a.center = c->center.i();
+  a.n_edges = (int)E;
+  a.src_ptr = c->src_ptr.i();
+  a.src_perm = c->src_perm.i();
+  a.dh = c->dh.f();  // the last block writes its dE/dx rows here
+  a.dxc = (!last && t > 0) ? c->dxc.f() : nullptr;
+  a.dgu = c->dgu.f();
+  a.demb = c->demb.f();
+  a.W = mlp_ptrs(m, t);
+  a.n_centers = (int)nl;
+  a.n_nodes = (int)n;
+  // part 0: boundary centres / their edges / ghost neighbour nodes
+  a.c_begin = (int)(part == 0 ? n_int : 0);
+  a.c_end = (int)(part == 0 ? nl : n_int);
+  a.node_begin = (int)(part == 0 ? nl : 0);
+  a.node_end = (int)(part == 0 ? n : nl);
+  double ef = (double)(part == 0 ? E - e_int : e_int);
+  if (last && c->timing && a.node_end > a.node_begin) {
+    // the last block's launch covers the edges of its neighbour-node range
+    int32_t q[2];
+    HIPCHK(hipMemcpyAsync(&q[0], a.src_ptr + a.node_begin, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&q[1], a.src_ptr + a.node_end, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    ef = (double)(q[1] - q[0]);
+  }
+  // empty ranges launch nothing (and are not counted as launches)
+  if (last ? a.node_end > a.node_begin : a.c_end > a.c_begin) {
+    // algorithmic FLOP (the forward radial MLP the kernel recomputes is not
+    // counted): dE/dx + dE/dY = 2 x TP; dE/dw = TP, dH2 = dw W2^T, MLP chain
+    const double xf = 3.0 * tp_flops_per_edge(code) + 2.0 * (64 * W + 64 * 64 + 8 * 64);
+    Region r(c, s, C_CONV_BWD_X + kind, xf * ef,
+             ef * 4 * (8 + 9 + 2 + 3 + 8) + (a.c_end - a.c_begin) * 4.0 * dm);
+    HIPCHK(last ? launch_conv_bwd_nbr_last(code, a, s) : launch_conv_bwd_ls(code, a, s));
+  }
+  // rows of this part: ghosts [nl, n) in part 0, owned [0, nl) in part 1
+  return part == 0 ? in_bwd(nl, n, !last, false) : in_bwd(0, nl, !last, true);
 }
 
 int e3gnn_layer_backward(e3gnn_ctx* c, int t, void* stream) {

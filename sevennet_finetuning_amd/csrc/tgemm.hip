@@ -26,9 +26,6 @@
 #include "common.h"
 #include "tgemm.h"
 
-#include <cstdio>
-#include <cstdlib>
-
 namespace e3gnn {
 namespace {
 
@@ -351,28 +348,18 @@ __global__ __launch_bounds__(256) void k_tgemm_reduce(TgRedBatch batch) {
 
 }  // namespace
 
-// split-K policy (E3GNN_TG_SPLIT="min_ksteps,target_wgs,ksteps_per_split" for
-// A/B timing, in 64 x 64 x 16 tile steps): split only a long K (the extra
-// reduction launch costs ~5 us).  E3GNN_TG_SMALL: problems with fewer
-// (64 x 64 tiles x splits) than this take the 32 x 32 x 32 k-split tiles
-static int tg_policy(int i) {
-  static int v[5] = {-1, -1, -1, -1, -1};
-  if (v[0] < 0) {
-    v[0] = 32, v[1] = 1024, v[2] = 8, v[3] = 256, v[4] = 0;
-    if (const char* e = std::getenv("E3GNN_TG_SPLIT")) std::sscanf(e, "%d,%d,%d", &v[0], &v[1], &v[2]);
-    if (const char* e = std::getenv("E3GNN_TG_SMALL")) v[3] = std::atoi(e);
-    if (const char* e = std::getenv("E3GNN_TG_SMALL_SPLIT")) v[4] = std::atoi(e);
-  }
-  return v[i];
-}
+// split-K policy, in 64 x 64 x 16 tile steps: split only a long K (the extra
+// reduction launch costs ~5 us) into ~TG_TARGET_WGS workgroups of at least
+// TG_KSTEPS_PER_SPLIT k-steps each.  Unsplit problems with fewer 64 x 64
+// tiles than TG_SMALL_TILES take the 32 x 32 x 32 k-split tiles
+constexpr int TG_MIN_KSTEPS = 32, TG_TARGET_WGS = 1024, TG_KSTEPS_PER_SPLIT = 8, TG_SMALL_TILES = 256;
 int tg_splits(int64_t M, int64_t N, int64_t K) {
   const int64_t tiles = ((M + 63) / 64) * ((N + 63) / 64);
   const int64_t nk = (K + 15) / 16;
   // few output tiles and a long K (the edge-summed weight gradients: K = 2E
-  // ~ 24k rows onto 64 x 960 outputs): split K so the launch has ~target
-  // workgroups of >= ksteps_per_split k-steps each
-  if (tiles >= tg_policy(1) / 2 || nk < tg_policy(0)) return 1;
-  int64_t s = std::min<int64_t>((tg_policy(1) + tiles - 1) / tiles, nk / tg_policy(2));
+  // ~ 24k rows onto 64 x 960 outputs)
+  if (tiles >= TG_TARGET_WGS / 2 || nk < TG_MIN_KSTEPS) return 1;
+  int64_t s = std::min<int64_t>((TG_TARGET_WGS + tiles - 1) / tiles, nk / TG_KSTEPS_PER_SPLIT);
   return (int)std::max<int64_t>(1, std::min<int64_t>(s, 256));
 }
 
@@ -381,8 +368,8 @@ bool tg_add(TgBatch& b, TgProb p) {
   if (p.M == 0 || p.N == 0) return true;
   if (p.K2 == 0) p.A2 = p.A1, p.B2 = p.B1, p.A2.ks = p.B2.ks = 0;   // no second pair
   if (p.splits < 1) p.splits = 1;
-  p.mode = ((int64_t)((p.M + 63) / 64) * ((p.N + 63) / 64) * p.splits < tg_policy(3) &&
-            (p.splits == 1 || tg_policy(4))) ? 1 : 0;
+  p.mode = ((int64_t)((p.M + 63) / 64) * ((p.N + 63) / 64) * p.splits < TG_SMALL_TILES &&
+            p.splits == 1) ? 1 : 0;
   const int BM = p.mode ? 32 : 64, BK = p.mode ? TG_M1_BK : 16;
   auto steps = [BK](int K, const TgLay& a, const TgLay& b) {
     if (K <= 0) return 0;

@@ -102,7 +102,6 @@ class _Linear:
     # the flat weight (each element repeated 2l+1 times) and a scatter to unique
     # positions -- no index with millions of duplicates (a gather from a zero pad
     # slot that way faulted inside a captured graph's backward on the GPU).
-    dense = os.environ.get('E3GNN_TRAIN_DENSE_LINEAR', '1') != '0'
 
     def _dense_maps(self, device, dtype):
         key = (str(device), dtype)
@@ -134,8 +133,7 @@ class _Linear:
         n = x.shape[0]
         # (dense only where the expanded matrix stays small: <= 4M entries, and
         # while the zeros' extra FLOPs are cheap against the launches saved)
-        if self.dense and len(self.x_sizes) > 1 and \
-                self.in_off[-1] * self.out_off[-1] <= (1 << 22) and n <= 65536:
+        if len(self.x_sizes) > 1 and self.in_off[-1] * self.out_off[-1] <= (1 << 22) and n <= 65536:
             return x @ self._dense_weight(w_flat)
         xs = x.split(self.x_sizes, dim=1) if len(self.x_sizes) > 1 else (x,)
         ws = w_flat.split(self.w_sizes) if len(self.w_sizes) > 1 else (w_flat,)

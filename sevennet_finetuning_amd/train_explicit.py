@@ -126,9 +126,7 @@ class _Gemms:
     transposed view (``W.t()``) is passed as op(X) = X^T of its storage."""
 
     def __init__(self, model):
-        # E3GNN_TRAIN_TGEMM=0: torch's GEMMs (A/B)
-        on = model.flat.is_cuda and os.environ.get('E3GNN_TRAIN_TGEMM', '1') != '0'
-        self.lib = model._act_lib() if on else None
+        self.lib = model._act_lib() if model.flat.is_cuda else None
         self.q = []
         self.ws = None
         self.max_probs = 12        # e3gnn_gemm_grouped's problems per launch
@@ -782,30 +780,6 @@ class ExplicitStep:
                     (f'si2{t}', blk['si2'], f'{t}_self_interaction_2.linear.weight')]
         ent += [('r1', model.readout1, 'reduce_input_to_hidden.linear.weight'),
                 ('r2', model.readout2, 'reduce_hidden_to_energy.linear.weight')]
-        # si2 (mid irreps -> gate input) is block-diagonal by l: ~10x zeros in
-        # its dense matrix.  Its products per instruction block (strided views,
-        # E3GNN_TRAIN_SI2_BLOCKS=1) measured SLOWER at the fine-tune batch size
-        # (10.05-10.2 vs 8.14 ms per step, same box): three small strided GEMMs
-        # cost more than one dense one.  Default: one dense product per use.
-        self.si2_blocks = []
-        dense_si2 = os.environ.get('E3GNN_TRAIN_SI2_BLOCKS', '0') != '1'
-        for t, blk in enumerate(model.blocks):
-            lin = blk['si2']
-            bl = [(lin.in_off[i], lin.in_off[i] + lin.irreps_in[i][0] * (2 * lin.irreps_in[i][1] + 1),
-                   lin.out_off[j], lin.out_off[j] + lin.irreps_out[j][0] * (2 * lin.irreps_out[j][1] + 1))
-                  for i, j in lin.ins]
-            if dense_si2:
-                bl = [(0, lin.in_off[-1], 0, lin.out_off[-1])]
-            cover = sorted({(a, b) for a, b, _, _ in bl})
-            gaps, pos = [], 0
-            for a, b in cover:
-                if a > pos:
-                    gaps.append((pos, a))
-                pos = max(pos, b)
-            if pos < lin.in_off[-1]:
-                gaps.append((pos, lin.in_off[-1]))
-            self.si2_blocks.append((bl, gaps))
-        self.dense_si2 = dense_si2
         # frozen convolution denominators (the default) are folded into si2:
         # agg / den W = agg (W / den), and the si2 gradient divided by den in
         # the flush -- no division launches on the activations
@@ -838,12 +812,12 @@ class ExplicitStep:
         self.mlp_buf = torch.empty(off, device=dev, dtype=dt)
         # layer 2 of the forward / tangent chains on bf16x6 matrix cores
         # (e3gnn_radial_mlp_forward_p): the W2 piece images, rebuilt by one
-        # launch with the weights (E3GNN_TRAIN_MLP_BF16=0: the f32 chains)
+        # launch with the weights (the f32 chains: widths that are no multiple
+        # of 16, more than 8 blocks)
         self.w2p = None
         self._w2p_of = {}
         widths = [views[2][1][1] for views in self.mlp_views]
-        if (self.p._hip(self.mlp_buf) and os.environ.get('E3GNN_TRAIN_MLP_BF16', '1') != '0'
-                and all(w % 16 == 0 for w in widths) and len(widths) <= 8):
+        if self.p._hip(self.mlp_buf) and all(w % 16 == 0 for w in widths) and len(widths) <= 8:
             lib = self.p.lib
             nb = [int(lib.e3gnn_radial_mlp_w2_piece_bytes(w)) for w in widths]
             offs = np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
@@ -1024,33 +998,14 @@ class ExplicitStep:
         self._kr_cache[ck] = res
         return res
 
-    # ---- si2 products over its instruction blocks (views, no copies)
-    def _si2_fwd(self, t, A, Dm, out):
-        """out += A Dm (the gate-input rows)"""
-        for i0, i1, o0, o1 in self.si2_blocks[t][0]:
-            out[:, o0:o1].addmm_(A[:, i0:i1], Dm[i0:i1, o0:o1])
-
     def _si2_t(self, t, A, Dm):
         """A Dm^T (cotangent rows of the mid irreps)"""
-        if self.dense_si2:
-            return self._lin(torch.empty(A.shape[0], Dm.shape[0], device=A.device, dtype=A.dtype),
-                             A, f'si2{t}', trans=True)
-        bl, gaps = self.si2_blocks[t]
-        out = torch.empty(A.shape[0], Dm.shape[0], device=A.device, dtype=A.dtype)
-        seen = set()
-        for i0, i1, o0, o1 in bl:
-            out[:, i0:i1].addmm_(A[:, o0:o1], Dm[i0:i1, o0:o1].t(),
-                                 beta=1.0 if (i0, i1) in seen else 0.0)
-            seen.add((i0, i1))
-        for a, b in gaps:
-            out[:, a:b].zero_()
-        return out
-
-    def _si2_wgrad(self, t, Gm, A, B):
-        """Gm += A^T B on si2's blocks (the other entries of the dense gradient
-        map to no weight)"""
-        for i0, i1, o0, o1 in self.si2_blocks[t][0]:
-            Gm[i0:i1, o0:o1].addmm_(A[:, i0:i1].t(), B[:, o0:o1])
+        # si2 (mid irreps -> gate input) is block-diagonal by l, ~10x zeros in
+        # its dense matrix, yet one dense product per use measured faster at
+        # the fine-tune batch size than a product per instruction block over
+        # strided views (8.14 vs 10.05-10.2 ms per step, same box)
+        return self._lin(torch.empty(A.shape[0], Dm.shape[0], device=A.device, dtype=A.dtype),
+                         A, f'si2{t}', trans=True)
 
     # ---- the radial MLP chains: one HIP launch each (e3gnn_radial_mlp_*) on
     # float32 device tensors, the same GEMMs + element-wise steps otherwise
@@ -1189,11 +1144,7 @@ class ExplicitStep:
             if not self.fold_den:            # (folded: D[si2] is si2 / den)
                 AGG[:n].div_(den)
             Yg = new(2 * n, D[f'si2{t}'].shape[1])
-            if self.dense_si2:                              # x sc + agg si2: one product
-                self._lin(Yg[:n], x, f'sc{t}', A2=AGG[:n], key2=f'si2{t}')
-            else:
-                self._mm(Yg[:n], x, D[f'sc{t}'])            # (GEMM into the output, then
-                self._si2_fwd(t, AGG[:n], D[f'si2{t}'], Yg[:n])  # accumulate: no bias copy)
+            self._lin(Yg[:n], x, f'sc{t}', A2=AGG[:n], key2=f'si2{t}')   # x sc + agg si2: one product
             Xn = new(2 * n, self.gates[t].dims[3] if self.gates[t].ng else Yg.shape[1])
             self.gates[t].fwd(Yg[:n], out=Xn[:n])
             blocks.append({'X': X, 'H': H, 'A1': A1, 'H1': H1, 'A2': A2, 'H2': H2, 'WT': WT,
@@ -1292,17 +1243,10 @@ class ExplicitStep:
                     be.forward(k, graph, hd, Y, w, out=aggd, acc=True)
             if not self.fold_den:
                 aggd.div_(b['den'])
-            if self.dense_si2:
-                if t > 0:
-                    self._lin(Yg[n:], X[n:], f'sc{t}', A2=AGG[n:], key2=f'si2{t}')
-                else:                            # x0' = 0
-                    self._lin(Yg[n:], AGG[n:], f'si2{t}')
-            else:
-                if t > 0:
-                    self._mm(Yg[n:], X[n:], D[f'sc{t}'])
-                else:
-                    Yg[n:].zero_()
-                self._si2_fwd(t, AGG[n:], D[f'si2{t}'], Yg[n:])
+            if t > 0:
+                self._lin(Yg[n:], X[n:], f'sc{t}', A2=AGG[n:], key2=f'si2{t}')
+            else:                                # x0' = 0
+                self._lin(Yg[n:], AGG[n:], f'si2{t}')
             Xn = blocks[t + 1]['X'] if t + 1 < len(blocks) else S['XL']
             self.gates[t].jvp(Yg[:n], Yg[n:], out=Xn[n:])
         XL = S['XL']
@@ -1341,18 +1285,13 @@ class ExplicitStep:
             Yg, AGG, X, H = b['Y'], b['AGG'], b['X'], b['H']
             YB = new(2 * n, Yg.shape[1])
             self.gates[t].dual_vjp(Yg[:n], Yg[n:], XB[:n], XB[n:], out0=YB[:n], out1=YB[n:])
-            if self.dense_si2:
-                # independent products of y-bar, one launch: si2's and sc's weight
-                # gradients and agg-bar
-                AGGB = new(2 * n, D[f'si2{t}'].shape[0])
-                self._lin_grad(G[f'si2{t}'], AGG, YB, f'si2{t}')
-                self._lin(AGGB, YB, f'si2{t}', trans=True, flush=False)
-                self._lin_grad(G[f'sc{t}'], X, YB, f'sc{t}')
-                self.gm.flush()
-            else:
-                self._si2_wgrad(t, G[f'si2{t}'], AGG, YB)
-                AGGB = self._si2_t(t, YB, D[f'si2{t}'])
-                self._mm(G[f'sc{t}'], X.t(), YB, beta=1)
+            # independent products of y-bar, one launch: si2's and sc's weight
+            # gradients and agg-bar
+            AGGB = new(2 * n, D[f'si2{t}'].shape[0])
+            self._lin_grad(G[f'si2{t}'], AGG, YB, f'si2{t}')
+            self._lin(AGGB, YB, f'si2{t}', trans=True, flush=False)
+            self._lin_grad(G[f'sc{t}'], X, YB, f'sc{t}')
+            self.gm.flush()
             gden = self._G(f'{pre}.denominator')
             if gden is not None:
                 gden.sub_(torch.dot(AGGB.view(-1), AGG.view(-1)) / b['den'])

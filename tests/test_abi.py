@@ -38,6 +38,28 @@ def test_build_lib_refuses_variants_as_the_product(tmp_path):
     assert r.returncode != 0 and '--out' in r.stderr
 
 
+def test_environment_switches_are_the_documented_ones():
+    """the run-time switches of the product: every E3GNN_* name the library
+    reads with getenv or the package reads through os.environ (DESIGN.md,
+    "Switches", says why each remains)"""
+    import glob
+    import os
+    import re
+    pkg = os.path.dirname(_lib.__file__)
+    names = set()
+    for ext in ('cpp', 'hip', 'h'):
+        for path in glob.glob(os.path.join(pkg, 'csrc', '*.' + ext)):
+            with open(path) as f:
+                names |= set(re.findall(r'getenv\(\s*"(E3GNN_[A-Z0-9_]+)"', f.read()))
+    for path in glob.glob(os.path.join(pkg, '*.py')):
+        with open(path) as f:
+            for line in f:
+                if 'os.environ' in line:
+                    names |= set(re.findall(r'''['"](E3GNN_[A-Z0-9_]+)['"]''', line))
+    assert names == {'E3GNN_LIB', 'E3GNN_GENERIC', 'E3GNN_NODELIN', 'E3GNN_D3_BIN', 'E3GNN_D3_NO_C6TAB',
+                     'E3GNN_TRACE_ERRORS', 'E3GNN_SYNC', 'E3GNN_TRAIN_IRREPS'}
+
+
 def test_abi_version_and_errors():
     lib = _lib.load()
     assert lib.e3gnn_abi_version() == 1

@@ -42,10 +42,8 @@ for s in "$@"; do
     traintests) step traintests 400 python -m pytest tests/test_gpu_train.py -x -q --timeout 200 --timeout-method thread ;;
     benchtrain) step benchtrain 300 python bench_train.py --steps 10 --warmup 3 ;;
     benchtrain2_*) step $s 300 python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    benchtrainsd) step benchtrainsd 300 env E3GNN_TRAIN_SI2_BLOCKS=0 python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
     benchtrainv_*) v=${s#benchtrainv_}; step benchtrain_$v 300 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
     benchtrain2) step benchtrain2 300 python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    benchtrainblk) step benchtrainblk 300 env E3GNN_TRAIN_DENSE_LINEAR=0 python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
     benchtrainlt) step benchtrainlt 300 python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline --blas hipblaslt ;;
     benchtrainag) step benchtrainag 300 python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline --autograd ;;
     proftrainx) step proftrainx 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_trainx -o run --output-format csv -- python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
@@ -61,7 +59,6 @@ for s in "$@"; do
     pmcf) step pmcf 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -o run -- python bench.py --steps 1 --warmup 1 --profile-only --no-parity-check ;;
     pmcmops) step pmcmops 900 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU --kernel-trace --output-format csv -d gpurun_out/pmc_mops -o run -- python bench.py --steps 1 --warmup 1 --profile-only --no-parity-check ;;
     pmcw) step pmcw 900 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -o run -- python bench.py --steps 1 --warmup 1 --profile-only --no-parity-check ;;
-    slp) step slp_build 600 env E3GNN_FUSED_FLAGS=" " python -c "import sevennet_finetuning_amd.build_lib as b; b.build(force=True)" && step benchslp 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline ;;
     ptest) step ptest 600 python -m pytest tests/test_parallel.py -q ;;
     bench2) step bench2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 2 --warmup 1 --cells 11 --same-device --no-cpu-baseline ;;
     report) step report 300 python tools/parity_report.py ;;
@@ -77,35 +74,20 @@ for s in "$@"; do
     proftracev_*) v=${s#proftracev_}; step proftrace_$v 600 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so rocprofv3 --kernel-trace --output-format csv -d gpurun_out/proftrace_$v -o run -- python bench.py --steps 1 --warmup 1 --profile-only --no-parity-check ;;
     testsv_*) v=${s#testsv_}; step testsv_$v 600 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python -u -m pytest tests/test_gpu_parity.py -x -q --timeout 300 --timeout-method thread ;;
     benchv_*) v=${s#benchv_}; step bench_$v 600 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-parity-check ;;
-    testsv_*) v=${s#testsv_}; step tests_$v 600 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python -m pytest tests -m gpu -x -q ;;
     bench2self) step bench2self 600 python bench.py --full --gpus 2 --same-device --steps 2 --warmup 1 --cells 11 --no-cpu-baseline ;;
     paritydef) step paritydef 600 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_fullsize.py -x -v --timeout 300 --timeout-method thread ;;
     stamps_*) v=${s#stamps_}; step stamps_$v 300 python tools/stamps.py sevennet_finetuning_amd/variants/$v.so ;;
     reportv_*) v=${s#reportv_}; step report_$v 300 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python tools/parity_report.py ;;
-    benchtrain_notg) step benchtrain_notg 300 env E3GNN_TRAIN_TGEMM=0 python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    benchtrain_nofl) step benchtrain_nofl 300 env E3GNN_TRAIN_FUSED_LOSS=0 python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    benchtrain_none) step benchtrain_none 300 env E3GNN_TRAIN_FUSED_LOSS=0 E3GNN_TRAIN_TGEMM=0 python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    btsplit_*) v=${s#btsplit_}; step btsplit_$v 300 env E3GNN_TG_SPLIT=${v//_/,} python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
     btdense) step btdense 300 env E3GNN_TRAIN_IRREPS=0 python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
     proftrainv_*) v=${s#proftrainv_}; step proftrain_$v 600 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so rocprofv3 --kernel-trace --stats -d gpurun_out/prof_train_$v -o run --output-format csv -- python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    btcg_*) v=${s#btcg_}; step btcg_$v 300 env E3GNN_MLP_FWD_CG=$v python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    btmlp_*) v=${s#btmlp_}; cg=${v%_*}; wt=${v#*_}; step btmlp_$v 600 env E3GNN_MLP_FWD_CG=$cg E3GNN_MLP_W2T=$wt rocprofv3 --kernel-trace --stats -d gpurun_out/prof_mlp_$v -o run --output-format csv -- python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    proftracenl_*) v=${s#proftracenl_}; step proftracenl_$v 600 env E3GNN_NL_BF16=$v rocprofv3 --kernel-trace --output-format csv -d gpurun_out/proftracenl_$v -o run -- python bench.py --steps 1 --warmup 1 --profile-only --no-parity-check ;;
-    benchnlm_*) v=${s#benchnlm_}; step benchnlm_$v 600 env E3GNN_NL_BF16=$v python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-parity-check ;;
     fullv_*) v=${s#fullv_}; step full_$v 900 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_fullsize.py -x -v --timeout 600 --timeout-method thread ;;
     tgb) step tgb 300 python tools/tgemm_bench.py --full ;;
-    tgbs_*) v=${s#tgbs_}; step tgbs_$v 300 env E3GNN_TG_SMALL=$v python tools/tgemm_bench.py ;;
-    btsmall_*) v=${s#btsmall_}; step btsmall_$v 300 env E3GNN_TG_SMALL=$v python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    btss_*) v=${s#btss_}; step btss_$v 300 env E3GNN_TG_SMALL_SPLIT=$v python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    tgbss_*) v=${s#tgbss_}; step tgbss_$v 300 env E3GNN_TG_SMALL_SPLIT=$v python tools/tgemm_bench.py ;;
     proftgb) step proftgb 600 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof_tgb -o run -- python tools/tgemm_bench.py --reps 3 --full ;;
     tgbv_*) v=${s#tgbv_}; step tgbv_$v 300 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python tools/tgemm_bench.py ;;
     btv_*) v=${s#btv_}; step btv_$v 300 env E3GNN_LIB=sevennet_finetuning_amd/variants/$v.so python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
     btkarg_*) v=${s#btkarg_}; step btkarg_$v 300 env HIP_FORCE_DEV_KERNARG=$v python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
     tgbkarg_*) v=${s#tgbkarg_}; step tgbkarg_$v 300 env HIP_FORCE_DEV_KERNARG=$v python tools/tgemm_bench.py ;;
     proftraint) step proftraint 600 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof_traint -o run -- python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    benchdxc_*) v=${s#benchdxc_}; step benchdxc_$v 600 env E3GNN_DXC_SORTED=$v python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-parity-check ;;
-    btmlpbf_*) v=${s#btmlpbf_}; step btmlpbf_$v 300 env E3GNN_TRAIN_MLP_BF16=$v python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
     gtrain) step gtrain 600 python -u -m pytest tests/test_gpu_train.py -x -q --timeout 300 --timeout-method thread ;;
     benchmc_*) v=${s#benchmc_}; step benchmc_$v 600 python bench.py --full --model-config $v --steps 5 --warmup 2 --no-cpu-baseline ;;
     proftrain2) step proftrain2 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_train2 -o run --output-format csv -- python bench_train.py --steps 10 --warmup 3 --no-cpu-baseline ;;
