@@ -164,7 +164,9 @@ int e3gnn_ewc_flat(int64_t n, const float* theta, const float* f, const float* o
 /* Which engine serves the deployment: the channel family of the fused
  * radial-MLP + tensor-product kernels (>= 0: 0 SevenNet-0's 128x0e+64x1e+32x2e,
  * 1 uniform 64, 2 uniform 32 channels; lmax 2, even parity, XPLOR, linear
- * self-connection, 8 Bessel, 64-64 radial MLP, any number of blocks >= 2), or
+ * self-connection, 8 Bessel, 64-64 radial MLP, any number of blocks >= 2; with
+ * or without linear biases, a linear readout or an FCN readout of 1-4 hidden
+ * layers up to 128 wide), or
  * -1: the generic runtime-path-table engine (every other nequip-family model). */
 int e3gnn_model_family(const e3gnn_model* m);
 

@@ -24,9 +24,11 @@
 #include <vector>
 
 #include "../../include/e3gnn.h"
+#include "bias_row.h"
 #include "cg_tables.h"
 #include "d3.h"
 #include "dbuf.h"
+#include "fcn_act.h"
 #include "generic.h"
 #include "train_ops.h"
 #include "common.h"
@@ -167,6 +169,16 @@ struct e3gnn_model {
   std::vector<float> denom;
   DBuf coeffs, embed, readout_v, scale, shift;
   std::vector<std::unique_ptr<Linear>> sc, si1, si2;
+  // use_bias_in_linear: the full-width bias rows of si1 (dim(irreps[t])) and
+  // si2 (dim(gin[t]): scalars and gates), nonzero on the 0e columns; null
+  // without biases.  The embedding's bias sits in `embed`, the linear
+  // readout's constant in `shift`.
+  std::vector<DBuf> b_si1, b_si2;
+  // readout_as_fcn: the FCN readout's dims and packed weights (node.h
+  // FcnDims); readout_v is not built
+  bool fcn = false;
+  FcnDims fcnd{};
+  DBuf fcn_w;
   // k_nodelin problem sets: si1, si1^T, si2^T, si2 + sc (forward, gate
   // epilogue), si1^T + sc^T (backward)
   std::vector<std::unique_ptr<LinPair>> nl_si1, nl_si1t, nl_si2t, nl_fwd, nl_bwd;
@@ -655,10 +667,22 @@ int fused_family(const minijson::Value& man) {
   if (lmax != 2) return -1;
   if (man.has("self_connection_type") && man["self_connection_type"].str() != "linear") return -1;
   if (!man.has("cutoff_function") || man["cutoff_function"]["name"].str() != "XPLOR") return -1;
-  // linear biases / the FCN readout (model_build.py:194-240, :396-408): the
-  // generic engine applies them
-  if (man.has("use_bias_in_linear") && man["use_bias_in_linear"].boolean()) return -1;
-  if (man.has("readout") && man["readout"].has("type") && man["readout"]["type"].str() != "linear") return -1;
+  // linear biases (model_build.py:194-240) ride in the node-linear epilogues
+  // and the FCN readout (:396-408) has its own kernel (node.hip
+  // k_readout_fcn), within its limits: 1 .. FCN_MAX_HIDDEN hidden layers of
+  // 1 .. FCN_MAX_WIDTH units and one of fcn_act.h's activations.  Beyond them
+  // the generic engine serves the model.
+  if (man.has("readout") && man["readout"].has("type") && man["readout"]["type"].str() != "linear") {
+    const auto& ro = man["readout"];
+    if (ro["type"].str() != "fcn" || !ro.has("hidden") || !ro.has("act") || !ro.has("act_norm")) return -1;
+    const auto& h = ro["hidden"].arr();
+    if (h.size() < 1 || h.size() > (size_t)FCN_MAX_HIDDEN) return -1;
+    for (auto& w : h)
+      if (w.num() < 1 || w.num() > FCN_MAX_WIDTH || w.num() != std::floor(w.num())) return -1;
+    bool known = false;
+    for (int k = 0; k < FCN_ACT_KINDS; ++k) known = known || ro["act"].str() == fcn_act_names()[k];
+    if (!known) return -1;
+  }
   const int L = (int)man["num_convolution_layer"].num();
   if (L < 2) return -1;
   if (man.has("weight_nn_hidden_neurons")) {
@@ -792,25 +816,77 @@ e3gnn_model* e3gnn_load(const char* weights_path, const char* manifest_path, int
     const float* we = get("onehot_to_feature_x.linear.weight", (size_t)m->nsp * d0);
     std::vector<float> emb((size_t)m->nsp * d0);
     for (size_t i = 0; i < emb.size(); ++i) emb[i] = (float)(we[i] / std::sqrt((double)m->nsp));
-    if (upload(m->embed, emb) != hipSuccess) throw std::runtime_error("upload");
-    // two linears without activation (D x0e -> H x0e -> 1x0e) folded into one
-    // vector, e3nn path weights 1 / sqrt(fan_in) each
-    const int dl = irreps_dim(m->irreps[m->nlayer]);
-    const int hid = (int)numel("reduce_hidden_to_energy.linear.weight");
-    const float* wh = get("reduce_input_to_hidden.linear.weight", (size_t)dl * hid);
-    const float* wo = get("reduce_hidden_to_energy.linear.weight", hid);
-    std::vector<float> v(dl);
-    for (int c = 0; c < dl; ++c) {
-      double s = 0;
-      for (int k = 0; k < hid; ++k) s += (double)wh[c * hid + k] * wo[k];
-      v[c] = (float)(s / (std::sqrt((double)dl) * std::sqrt((double)hid)));
+    // use_bias_in_linear: a bias tensor's full-width row over `out` (bias_row.h)
+    const bool has_bias = man.has("use_bias_in_linear") && man["use_bias_in_linear"].boolean();
+    auto bias = [&](const std::string& n, const Irreps& out) {
+      const float* b = get(n);   // (present and inside the file)
+      return bias_row(out, [](const Irr& i) { return i.l == 0; }, b, numel(n), n);
+    };
+    if (has_bias) {
+      // the embedding's bias: the same for every species row (k_embed copies rows)
+      const auto row = bias("onehot_to_feature_x.linear.bias", m->irreps[0]);
+      for (int sp = 0; sp < m->nsp; ++sp)
+        for (int c = 0; c < d0; ++c) emb[(size_t)sp * d0 + c] += row[c];
     }
-    if (upload(m->readout_v, v) != hipSuccess) throw std::runtime_error("upload");
-    trace_point("load:readout");
+    if (upload(m->embed, emb) != hipSuccess) throw std::runtime_error("upload");
+    const int dl = irreps_dim(m->irreps[m->nlayer]);
     const float* sc = get("rescale_atomic_energy.scale", m->nsp);
     const float* sh = get("rescale_atomic_energy.shift", m->nsp);
+    std::vector<float> shift(sh, sh + m->nsp);
+    m->fcn = man.has("readout") && man["readout"].has("type") && man["readout"]["type"].str() == "fcn";
+    if (m->fcn) {
+      // FCN_e3nn (nn/linear.py:94-129): e3nn FullyConnectedNet([dl] + hidden +
+      // [1], act), every layer's weight / sqrt(fan_in); packed in the order
+      // of node.h FcnDims (the hidden matrices with their odd row strides,
+      // then the output vector).  (fused_family checked the limits.)
+      const auto& ro = man["readout"];
+      FcnDims& fd = m->fcnd;
+      fd.nh = (int)ro["hidden"].arr().size();
+      fd.w[0] = dl;
+      for (int k = 0; k < fd.nh; ++k) fd.w[k + 1] = (int)ro["hidden"].arr()[k].num();
+      fd.kind = -1;
+      for (int k = 0; k < FCN_ACT_KINDS; ++k)
+        if (ro["act"].str() == fcn_act_names()[k]) fd.kind = k;
+      fd.c = (float)ro["act_norm"].num();
+      if (fd.kind < 0 || dl > FCN_MAX_WIDTH) throw std::runtime_error("readout FCN outside the kernel's limits");
+      std::vector<float> pk(fd.padded_floats(), 0.f);
+      for (int k = 0; k <= fd.nh; ++k) {
+        const int a = fd.w[k], b = k < fd.nh ? fd.w[k + 1] : 1;
+        const float* w = get("readout_FCN.fcn.layer" + std::to_string(k) + ".weight", (size_t)a * b);
+        const double sn = 1.0 / std::sqrt((double)a);
+        float* M = pk.data() + fd.mat_off(k);
+        const int ld = k < fd.nh ? fd.stride(k) : 1;
+        for (int i = 0; i < a; ++i)
+          for (int j = 0; j < b; ++j) M[(size_t)i * ld + j] = (float)(w[(size_t)i * b + j] * sn);
+      }
+      if (upload(m->fcn_w, pk) != hipSuccess) throw std::runtime_error("upload");
+    } else {
+      // two linears without activation (D x0e -> H x0e -> 1x0e) folded into one
+      // vector, e3nn path weights 1 / sqrt(fan_in) each
+      const int hid = (int)numel("reduce_hidden_to_energy.linear.weight");
+      const float* wh = get("reduce_input_to_hidden.linear.weight", (size_t)dl * hid);
+      const float* wo = get("reduce_hidden_to_energy.linear.weight", hid);
+      std::vector<float> v(dl);
+      for (int c = 0; c < dl; ++c) {
+        double s = 0;
+        for (int k = 0; k < hid; ++k) s += (double)wh[c * hid + k] * wo[k];
+        v[c] = (float)(s / (std::sqrt((double)dl) * std::sqrt((double)hid)));
+      }
+      if (upload(m->readout_v, v) != hipSuccess) throw std::runtime_error("upload");
+      if (has_bias) {
+        // e = (x A + bA) B + bB = x . v + c, c = bA . B / sqrt(hid) + bB, per
+        // atom before the rescale: shift[t] += scale[t] c (k_readout unchanged)
+        const Irreps hir{{hid, 0}}, one{{1, 0}};
+        const auto bh = bias("reduce_input_to_hidden.linear.bias", hir);
+        const auto bo = bias("reduce_hidden_to_energy.linear.bias", one);
+        double cst = bo[0];
+        for (int k = 0; k < hid; ++k) cst += (double)bh[k] * wo[k] / std::sqrt((double)hid);
+        for (int t = 0; t < m->nsp; ++t) shift[t] = (float)(shift[t] + cst * sc[t]);
+      }
+    }
+    trace_point("load:readout");
     if (upload(m->scale, std::vector<float>(sc, sc + m->nsp)) != hipSuccess ||
-        upload(m->shift, std::vector<float>(sh, sh + m->nsp)) != hipSuccess)
+        upload(m->shift, shift) != hipSuccess)
       throw std::runtime_error("upload");
     // interaction blocks
     for (int t = 0; t < m->nlayer; ++t) {
@@ -865,6 +941,16 @@ e3gnn_model* e3gnn_load(const char* weights_path, const char* manifest_path, int
       m->si1.push_back(mk(p + "_self_interaction_1.linear.weight", xin, xin, 1.0));
       // backward of si2 feeds dE/dagg_raw = dE/dagg / denominator (convolution.py:117-118)
       m->si2.push_back(mk(p + "_self_interaction_2.linear.weight", mid, gin, 1.0 / den));
+      // their biases (the self-connection has none, model_build.py:281-282):
+      // si2's covers the scalars and the gate pre-activations, and is not
+      // divided by the denominator (only si2's weights carry it)
+      m->b_si1.emplace_back();
+      m->b_si2.emplace_back();
+      if (has_bias) {
+        if (upload(m->b_si1[t], bias(p + "_self_interaction_1.linear.bias", xin)) != hipSuccess ||
+            upload(m->b_si2[t], bias(p + "_self_interaction_2.linear.bias", gin)) != hipSuccess)
+          throw std::runtime_error("upload");
+      }
       auto pair = [&](const Linear& a, bool ta, const Linear* b, bool tb) {
         auto P = std::make_unique<LinPair>();
         if (build_pair(*P, a, ta, b, tb) < 0) throw std::runtime_error("upload");
@@ -1439,10 +1525,16 @@ int e3gnn_layer_forward_part(e3gnn_ctx* c, int t, int part, void* stream) {
     const float* x = c->x[t].f() + r0 * dx;
     float* h = c->h[t].f() + r0 * dx;
     NlBatch nb;
-    if (c->nodelin && nl_batch(nb, *m->nl_si1[t], x, dx, nullptr, 0, h, dx, r1 - r0, 0))
+    const float* b1 = m->b_si1[t].f();   // use_bias_in_linear: on the 0e block
+    auto bias_fix = [&](NlProb& q, const PairBlock& k) {
+      if (b1 && k.l == 0) q.bias = b1 + k.out_off;
+    };
+    if (c->nodelin && nl_batch(nb, *m->nl_si1[t], x, dx, nullptr, 0, h, dx, r1 - r0, 0, 0, bias_fix)) {
       HIPCHK(launch_nodelin(nb, s));
-    else
+    } else {
       HIPCHK(launch_gemm(lin_fwd(*m->si1[t], x, dx, h, dx, r1 - r0, 0), s));
+      if (b1) HIPCHK(launch_row_bias(r1 - r0, dx, b1, h, s));
+    }
     return E3GNN_OK;
   };
   // fused radial MLP + tensor product + segmented sum (fused.hip) of the
@@ -1496,6 +1588,9 @@ int e3gnn_layer_forward_part(e3gnn_ctx* c, int t, int part, void* stream) {
       q.ldxo = irreps_dim(xo);
       if (k.l == 0) {
         q.n_act = nscal;
+        // si2's bias on the scalars and the gates: C keeps the biased
+        // pre-activations the backward differentiates at
+        if (m->b_si2[t].f()) q.bias = m->b_si2[t].f() + k.out_off;
         return;
       }
       int off = gin[0].mul, gmul = 0, gdim = 0;
@@ -1521,6 +1616,7 @@ int e3gnn_layer_forward_part(e3gnn_ctx* c, int t, int part, void* stream) {
     Region r(c, s, C_LINEAR, lin_flops(*m->si2[t], nl) + lin_flops(*m->sc[t], nl));
     HIPCHK(launch_gemm(lin_fwd(*m->si2[t], c->agg.f(), dm, c->y[t].f(), dg, nl, 0), s));
     HIPCHK(launch_gemm(lin_fwd(*m->sc[t], c->x[t].f(), dx, c->y[t].f(), dg, nl, 1), s));
+    if (m->b_si2[t].f()) HIPCHK(launch_row_bias(nl, dg, m->b_si2[t].f(), c->y[t].f(), s));
   }
   {
     Region r(c, s, C_GATE_FWD, 0, nl * 4.0 * (dg + irreps_dim(m->irreps[t + 1])));
@@ -1548,14 +1644,27 @@ int e3gnn_readout(e3gnn_ctx* c, float* energy, float* atomic_energy, void* strea
   const int L = m->nlayer;
   {
     const int dl = irreps_dim(m->irreps[L]);
-    Region r(c, s, C_READOUT, 2.0 * nl * dl, nl * 4.0 * (dl + 2));
-    HIPCHK(launch_readout((int)nl, dl, c->x[L].f(), m->readout_v.f(), c->type.i(), m->scale.f(),
-                          m->shift.f(), c->eat.f(), s));
+    const FcnDims& fd = m->fcnd;
+    double flops = 2.0 * nl * dl, bytes = nl * 4.0 * (dl + 2);
+    if (m->fcn) {   // forward and backward of every layer; x[L] in, dE/dx[L] out
+      double mac = fd.w[fd.nh];
+      for (int k = 0; k < fd.nh; ++k) mac += (double)fd.w[k] * fd.w[k + 1];
+      flops = 4.0 * nl * mac;
+      bytes = nl * 4.0 * (2 * dl + 2);
+    }
+    Region r(c, s, C_READOUT, flops, bytes);
+    if (m->fcn)   // the FCN readout with its backward in one launch: eat and dE/dx[L]
+      HIPCHK(launch_readout_fcn((int)nl, fd, c->x[L].f(), m->fcn_w.f(), c->type.i(), m->scale.f(),
+                                m->shift.f(), c->eat.f(), c->grad[L].f(), s));
+    else
+      HIPCHK(launch_readout((int)nl, dl, c->x[L].f(), m->readout_v.f(), c->type.i(), m->scale.f(),
+                            m->shift.f(), c->eat.f(), s));
     HIPCHK(launch_sum(nl, c->eat.f(), c->part.f(), energy ? energy : c->scratch6.f(), s));
     if (atomic_energy && nl > 0)
       HIPCHK(hipMemcpyAsync(atomic_energy, c->eat.p, nl * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(launch_readout_bwd((int)nl, dl, m->readout_v.f(), c->type.i(), m->scale.f(),
-                              c->grad[L].f(), s));
+    if (!m->fcn)
+      HIPCHK(launch_readout_bwd((int)nl, dl, m->readout_v.f(), c->type.i(), m->scale.f(),
+                                c->grad[L].f(), s));
   }
   c->readout_done = 1;
   return E3GNN_OK;

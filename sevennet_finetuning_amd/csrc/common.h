@@ -134,11 +134,14 @@ hipError_t launch_gemm(const GemmBatch& b, hipStream_t s);
 // col < n_act (gate scalars / last block), 3 store + xo[node, xo_off + col * R
 // + m] = act(C[node, gate_off + col]) * v (gated irreps; the gate columns were
 // stored by an earlier launch).
+// bias (use_bias_in_linear; R == 1 only, null: none): v += bias[col] before the
+// store to C and before the activation -- C holds the biased pre-activations.
 struct NlProb {
   const float* A;
   const float* A2;
   const float* B;
   const void* Bb;  // B as bf16 pieces (LinPair::Wb order): k_nodelin_b; null: k_nodelin
+  const float* bias;  // the block's bias row (column 0 of the block first), 16-byte aligned
 
   float* C;
   float* xo;
@@ -156,7 +159,8 @@ struct NlBatch {
   int total_tiles;
 };
 // false when the problem does not meet the kernel's layout assumptions
-// (16-byte alignment of rows / offsets, K1 % 32 when split, R in {1, 3, 5})
+// (16-byte alignment of rows / offsets, K1 % 32 when split, R in {1, 3, 5},
+// a bias on an R == 1 problem only)
 bool add_nl(NlBatch& b, const NlProb& p);
 hipError_t launch_nodelin(const NlBatch& b, hipStream_t s);
 

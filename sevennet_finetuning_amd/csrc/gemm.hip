@@ -153,6 +153,22 @@ constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr int NL_LDS =
     2 * cmax(NlShape<1, 1>::STAGE, cmax(NlShape<2, 1>::STAGE, NlShape<2, 2>::STAGE));
 
+// The bias row of this workgroup's problem (NlProb::bias), read from the
+// kernel arguments where the epilogue needs it: NlBatch is the only argument of
+// k_nodelin / k_nodelin_b, so it starts the kernarg segment.  Carried in the
+// kernels' copy of the problem, the pointer would stay live in two SGPRs over
+// the k loop, which costs SGPR spills on the bias-free path (k_nodelin_b: 0 ->
+// 14 spilled SGPRs and one more VGPR to hold them).
+__device__ __forceinline__ const float* nl_bias_arg() {
+  typedef const NlBatch __attribute__((address_space(4))) * KArg;
+  KArg b = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
+  int pi = 0;
+#pragma unroll 1
+  for (int i = 1; i < b->nprob; ++i)
+    if ((int)blockIdx.x >= b->p[i].tile_begin) pi = i;
+  return b->p[pi].bias;
+}
+
 // Gate epilogue (epi 2 / 3) through LDS, one 64- (or 32-) column chunk at a
 // time: each node's output is one contiguous run of CW * R floats, written as
 // float4 (the MFMA layout would scatter 4-byte stores R floats apart).  The
@@ -160,7 +176,7 @@ constexpr int NL_LDS =
 // on the wide tiles).  Starts with a barrier: the caller's LDS readers are done.
 template <int WN, int R>
 __device__ __forceinline__ void nl_epilogue(const NlProb& P, const f32x16& acc, int node0, int n0,
-                                            float* lds) {
+                                            float* lds, const float* bias) {
   constexpr int BM = 128 / WN, CW = 32 * WN;
   constexpr int T = BM / R, ROWS = T * R;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -192,6 +208,13 @@ __device__ __forceinline__ void nl_epilogue(const NlProb& P, const f32x16& acc, 
       v[q] = cl[q] < ncol ? Cs[(nl * R + m) * LDC + cl[q]] : 0.f;
     }
     if (cl[0] >= ncol) continue;
+    if constexpr (R == 1) {
+      if (bias) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (cl[q] < ncol) v[q] += bias[n0 + cl[q]];
+      }
+    }
     const bool full = cl[3] < ncol;
     const int64_t nrow = (int64_t)node * P.ldc;
     float* cp = P.C + nrow + P.c_off + n0 * R + j;
@@ -239,7 +262,8 @@ __device__ __forceinline__ void nl_epilogue(const NlProb& P, const f32x16& acc, 
 // tile's node nl, column c of the chunk, component m): the f32 (32x32) and
 // bf16x6 (16x16) accumulator layouts share the copy-out.
 template <int BM, int CW, int R, int LDSF, class Stage>
-__device__ __forceinline__ void nl_epi_runs(const NlProb& P, int node0, int n0, float* lds, Stage stage) {
+__device__ __forceinline__ void nl_epi_runs(const NlProb& P, int node0, int n0, float* lds, Stage stage,
+                                            const float* bias) {
   constexpr int T = BM / R;
   constexpr int RUN = CW * R, LDR = RUN + 4;  // 16-byte aligned node runs
   static_assert(T * LDR <= LDSF, "C runs must fit the LDS stages");
@@ -258,6 +282,15 @@ __device__ __forceinline__ void nl_epi_runs(const NlProb& P, int node0, int n0, 
     if (j >= len || node >= P.nodes) continue;
     float4 v = *reinterpret_cast<const float4*>(lds + nl * LDR + j);
     float4* cp = reinterpret_cast<float4*>(P.C + (int64_t)node * P.ldc + P.c_off + n0 * R + j);
+    if constexpr (R == 1) {  // element q is column n0 + j + q
+      if (bias) {
+        const float4 b = *reinterpret_cast<const float4*>(bias + n0 + j);
+        v.x += b.x;
+        v.y += b.y;
+        v.z += b.z;
+        v.w += b.w;
+      }
+    }
     if (P.epi == 1) {
       const float4 o = *cp;
       v.x += o.x;
@@ -285,9 +318,9 @@ __device__ __forceinline__ void nl_stage32(const f32x16& acc, float* L, int LDR)
 }
 template <int WN, int R>
 __device__ __forceinline__ void nl_epilogue_runs(const NlProb& P, const f32x16& acc, int node0,
-                                                 int n0, float* lds) {
-  nl_epi_runs<128 / WN, 32 * WN, R, NL_LDS>(P, node0, n0, lds,
-                                             [&](float* L, int LDR) { nl_stage32<WN, R>(acc, L, LDR); });
+                                                 int n0, float* lds, const float* bias) {
+  nl_epi_runs<128 / WN, 32 * WN, R, NL_LDS>(
+      P, node0, n0, lds, [&](float* L, int LDR) { nl_stage32<WN, R>(acc, L, LDR); }, bias);
 }
 
 // The gate epilogues (epi 2 / 3) in the same run form.  epi 2 (the 0e block,
@@ -300,7 +333,8 @@ __device__ __forceinline__ void nl_epilogue_runs(const NlProb& P, const f32x16& 
 // activations per float4).  Gate problems split K (si2 + self-connection), so
 // only the single-block (NS = 1) tiles instantiate it.
 template <int BM, int CW, int R, int LDSF, class Stage>
-__device__ __forceinline__ void nl_epi_gate(const NlProb& P, int node0, int n0, float* lds, Stage stage) {
+__device__ __forceinline__ void nl_epi_gate(const NlProb& P, int node0, int n0, float* lds, Stage stage,
+                                            const float* bias) {
   constexpr int T = BM / R;
   constexpr int RUN = CW * R, LDR = RUN + 4;
   constexpr int GS = R > 1 ? T * CW : 0, NG = (GS + 255) / 256;
@@ -336,7 +370,16 @@ __device__ __forceinline__ void nl_epi_gate(const NlProb& P, int node0, int n0, 
     const int nl = u / SEGC, j = 4 * (u - nl * SEGC);
     const int node = node0 + nl;
     if (j >= len || node >= P.nodes) continue;
-    const float4 v = *reinterpret_cast<const float4*>(lds + nl * LDR + j);
+    float4 v = *reinterpret_cast<const float4*>(lds + nl * LDR + j);
+    if constexpr (R == 1) {  // the biased pre-activations go to C and to the activation
+      if (bias) {
+        const float4 b = *reinterpret_cast<const float4*>(bias + n0 + j);
+        v.x += b.x;
+        v.y += b.y;
+        v.z += b.z;
+        v.w += b.w;
+      }
+    }
     *reinterpret_cast<float4*>(P.C + (int64_t)node * P.ldc + P.c_off + n0 * R + j) = v;
     float* xp = P.xo + (int64_t)node * P.ldxo + P.xo_off + n0 * R + j;
     if constexpr (R == 1) {  // epi 2: element q is column n0 + j + q
@@ -357,9 +400,9 @@ __device__ __forceinline__ void nl_epi_gate(const NlProb& P, int node0, int n0, 
 }
 template <int WN, int R>
 __device__ __forceinline__ void nl_epilogue_gate(const NlProb& P, const f32x16& acc, int node0,
-                                                 int n0, float* lds) {
-  nl_epi_gate<128 / WN, 32 * WN, R, NL_LDS>(P, node0, n0, lds,
-                                             [&](float* L, int LDR) { nl_stage32<WN, R>(acc, L, LDR); });
+                                                 int n0, float* lds, const float* bias) {
+  nl_epi_gate<128 / WN, 32 * WN, R, NL_LDS>(
+      P, node0, n0, lds, [&](float* L, int LDR) { nl_stage32<WN, R>(acc, L, LDR); }, bias);
 }
 
 // Operand loads through buffer descriptors based at the tile (a 32-bit lane
@@ -519,14 +562,15 @@ __device__ __forceinline__ void nl_tile(const NlProb& P, int local, float* lds) 
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[sub][i] += acc2[sub][i];
   }
+  const float* bias = R == 1 ? nl_bias_arg() : nullptr;
 #pragma unroll
   for (int sub = 0; sub < NS; ++sub) {
     if (P.epi <= 1)
-      nl_epilogue_runs<WN, R>(P, acc[sub], node0, n0 + sub * 32 * WN, lds);
+      nl_epilogue_runs<WN, R>(P, acc[sub], node0, n0 + sub * 32 * WN, lds, bias);
     else if (NS == 1 && (R > 1) == (P.epi == 3))
-      nl_epilogue_gate<WN, R>(P, acc[sub], node0, n0 + sub * 32 * WN, lds);
+      nl_epilogue_gate<WN, R>(P, acc[sub], node0, n0 + sub * 32 * WN, lds, bias);
     else
-      nl_epilogue<WN, R>(P, acc[sub], node0, n0 + sub * 32 * WN, lds);
+      nl_epilogue<WN, R>(P, acc[sub], node0, n0 + sub * 32 * WN, lds, bias);
   }
 }
 
@@ -774,10 +818,11 @@ __device__ __forceinline__ void nl_tile_b(const NlProb& P, int local, float* lds
           if (row < ROWS) L[nl * LDR + col * R + m] = acc[a][b][i];
         }
   };
+  const float* bias = R == 1 ? nl_bias_arg() : nullptr;
   if (P.epi <= 1)
-    nl_epi_runs<BM, BN, R, NB_LDSF>(P, node0, n0, lds, stage);
+    nl_epi_runs<BM, BN, R, NB_LDSF>(P, node0, n0, lds, stage, bias);
   else
-    nl_epi_gate<BM, BN, R, NB_LDSF>(P, node0, n0, lds, stage);
+    nl_epi_gate<BM, BN, R, NB_LDSF>(P, node0, n0, lds, stage, bias);
 }
 
 // ------------------------------------------------- skinny node linears
@@ -992,10 +1037,12 @@ bool add_nl(NlBatch& b, const NlProb& p) {
     return false;
   if (p.epi >= 2 && (!al(p.xo) || p.ldxo % 4 || p.xo_off % 4 || (p.epi == 2 && p.R != 1)))
     return false;
+  if (p.bias && (p.R != 1 || !al(p.bias))) return false;
   NlProb q = p;
   // skinny: K <= 64 onto N >= 128 columns (si2^T l > 0: 345 vs ~400 us per
   // launch on the f32 tiles; si1's N <= 64 blocks ran slower there: f32)
-  const bool skinny = p.Bb && p.K == p.K1 && p.K <= 64 && p.K % 4 == 0 && p.N >= 128 && p.epi == 0;
+  const bool skinny = p.Bb && p.K == p.K1 && p.K <= 64 && p.K % 4 == 0 && p.N >= 128 && p.epi == 0 &&
+                      !p.bias;   // (k_nodelin_s has its own copy-out, without the bias)
   // bf16x6 tiles for the wide scalar blocks: l = 0, K and N
   // >= 224 -- the 0e gate launch (K 352, N 224) and si2^T's 0e block (224 x
   // 224) are MFMA-bound on the f32 tiles (139 vs 185 us and 75 vs ~105 us per

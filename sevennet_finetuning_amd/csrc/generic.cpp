@@ -30,8 +30,10 @@
 #include <tuple>
 
 #include "../../include/e3gnn.h"
+#include "bias_row.h"
 #include "common.h"
 #include "dbuf.h"
+#include "fcn_act.h"
 #include "gtp.h"
 #include "minijson.h"
 #include "node.h"
@@ -115,21 +117,10 @@ struct GLin {
   int din = 0, dout = 0;
   DBuf W, WT;
 };
-// e3nn o3.Linear(biases=True) (use_bias_in_linear): the bias over the full
-// output row -- b on the channels of every 0e output irrep, in output order,
-// zero elsewhere
-std::vector<float> bias_row(const GIrreps& out, const float* b, size_t numel) {
-  const auto oo = goffsets(out);
-  std::vector<float> v(oo.back(), 0.f);
-  size_t k = 0;
-  for (size_t j = 0; j < out.size(); ++j)
-    if (out[j].l == 0 && out[j].p == 1)
-      for (int u = 0; u < out[j].mul; ++u) {
-        if (k >= numel) throw std::runtime_error("linear bias size mismatch");
-        v[oo[j] + u] = b[k++];
-      }
-  if (k != numel) throw std::runtime_error("linear bias size mismatch");
-  return v;
+// e3nn o3.Linear(biases=True) (use_bias_in_linear): the full-width bias row
+// (bias_row.h) of the even scalar output irreps
+std::vector<float> bias_row(const GIrreps& out, const float* b, size_t numel, const std::string& name) {
+  return e3gnn::bias_row(out, [](const GIrr& i) { return i.l == 0 && i.p == 1; }, b, numel, name);
 }
 void make_lin(GLin& L, const std::vector<float>& W, int din, int dout) {
   L.din = din;
@@ -295,7 +286,7 @@ GenModel* gen_load(const minijson::Value& man, const std::vector<float>& flat) {
     // the embedding's bias (use_bias_in_linear): the same for every species row
     if (T.count("onehot_to_feature_x.linear.bias")) {
       auto b = get("onehot_to_feature_x.linear.bias");
-      const auto row = bias_row(irr[0], b.first, b.second);
+      const auto row = bias_row(irr[0], b.first, b.second, "onehot_to_feature_x.linear.bias");
       for (int sp = 0; sp < m->nsp; ++sp)
         for (int c = 0; c < m->d0; ++c) e[(size_t)sp * m->d0 + c] += row[c];
     }
@@ -418,11 +409,11 @@ GenModel* gen_load(const minijson::Value& man, const std::vector<float>& flat) {
       make_lin(G.si2, dense_linear(mid, gin, w.first, w.second, 1.0 / den), G.dm, G.dg);
       if (T.count(p + "_self_interaction_1.linear.bias")) {
         auto b = get(p + "_self_interaction_1.linear.bias");
-        if (upload(G.b1, bias_row(xi, b.first, b.second)) != hipSuccess) throw std::runtime_error("upload");
+        if (upload(G.b1, bias_row(xi, b.first, b.second, p + "_self_interaction_1.linear.bias")) != hipSuccess) throw std::runtime_error("upload");
       }
       if (T.count(p + "_self_interaction_2.linear.bias")) {
         auto b = get(p + "_self_interaction_2.linear.bias");
-        if (upload(G.b2, bias_row(gin, b.first, b.second)) != hipSuccess) throw std::runtime_error("upload");
+        if (upload(G.b2, bias_row(gin, b.first, b.second, p + "_self_interaction_2.linear.bias")) != hipSuccess) throw std::runtime_error("upload");
       }
     }
     if (sc_type == "linear") {
@@ -495,10 +486,9 @@ GenModel* gen_load(const minijson::Value& man, const std::vector<float>& flat) {
       for (auto& i : irr[L])
         if (i.l != 0) throw std::runtime_error("readout_as_fcn needs a scalar-only last block");
       const auto& ro = man["readout"];
-      static const char* kinds[] = {"relu", "silu", "tanh", "sigmoid", "abs", "elu"};
       m->fcn_kind = -1;
-      for (int k = 0; k < 6; ++k)
-        if (ro["act"].str() == kinds[k]) m->fcn_kind = k;
+      for (int k = 0; k < FCN_ACT_KINDS; ++k)
+        if (ro["act"].str() == fcn_act_names()[k]) m->fcn_kind = k;
       if (m->fcn_kind < 0) throw std::runtime_error("readout activation " + ro["act"].str() + " is not built");
       m->fcn_c = (float)ro["act_norm"].num();
       m->fcn_w = {dl};
@@ -534,7 +524,7 @@ GenModel* gen_load(const minijson::Value& man, const std::vector<float>& flat) {
       double cst = 0;
       if (T.count("reduce_input_to_hidden.linear.bias")) {
         auto b = get("reduce_input_to_hidden.linear.bias");
-        const auto row = bias_row(hir, b.first, b.second);
+        const auto row = bias_row(hir, b.first, b.second, "reduce_input_to_hidden.linear.bias");
         for (int k = 0; k < hid; ++k) cst += (double)row[k] * B[k];
       }
       if (T.count("reduce_hidden_to_energy.linear.bias")) cst += *get("reduce_hidden_to_energy.linear.bias").first;

@@ -9,6 +9,7 @@
 // autograd, force_output.py:74-130).  Deterministic: one thread owns every
 // output it writes, sums run in a fixed order, no float atomics.
 #include "common.h"
+#include "fcn_act.h"
 #include "generic.h"
 
 namespace e3gnn {
@@ -268,40 +269,15 @@ __global__ void k_gen_bias(int64_t n, int d, const float* __restrict__ b, float*
 
 // ------------------------------------------------------------ readout FCN
 // FCN_e3nn (nn/linear.py:94-129): e3nn FullyConnectedNet's activation
-// c f(z) (c = normalize2mom(f)) and its derivative c f'(z).  kind: 0 relu,
-// 1 silu, 2 tanh, 3 sigmoid, 4 abs, 5 elu (sevenn/_const.py ACTIVATION)
-__device__ __forceinline__ void gen_act(int kind, float z, float& f, float& df) {
-  switch (kind) {
-    case 0: f = z > 0.f ? z : 0.f; df = z > 0.f ? 1.f : 0.f; break;
-    case 1: {
-      const float sg = 1.f / (1.f + __expf(-z));
-      f = z * sg;
-      df = sg * (1.f + z * (1.f - sg));
-      break;
-    }
-    case 2: {
-      const float t = tanhf(z);
-      f = t;
-      df = 1.f - t * t;
-      break;
-    }
-    case 3: {
-      const float sg = 1.f / (1.f + __expf(-z));
-      f = sg;
-      df = sg * (1.f - sg);
-      break;
-    }
-    case 4: f = fabsf(z); df = z > 0.f ? 1.f : (z < 0.f ? -1.f : 0.f); break;
-    default: f = z > 0.f ? z : expm1f(z); df = z > 0.f ? 1.f : __expf(z); break;
-  }
-}
+// c f(z) (c = normalize2mom(f)) and its derivative c f'(z); f and f' are
+// fcn_act(kind, z, f, df) of fcn_act.h, shared with the fused engine's readout
 // mode 0: a = c f(z); mode 1: g = g_in * c f'(z)
 __global__ void k_gen_fcn_act(int64_t n, int kind, float c, int mode, const float* __restrict__ z,
                               const float* __restrict__ gin, float* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float f, df;
-  gen_act(kind, z[i], f, df);
+  fcn_act(kind, z[i], f, df);
   out[i] = mode == 0 ? c * f : gin[i] * c * df;
 }
 

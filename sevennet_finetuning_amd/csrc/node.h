@@ -49,6 +49,32 @@ hipError_t launch_readout(int n, int D, const float* x, const float* v, const in
                           const float* scale, const float* shift, float* eat, hipStream_t s);
 hipError_t launch_readout_bwd(int n, int D, const float* v, const int* type, const float* scale,
                               float* dx, hipStream_t s);
+// y[n, d] += b[d] on every row: the linear biases (use_bias_in_linear) after
+// the k_gemm fallback of the node linears (api.cpp); no launch for n == 0
+hipError_t launch_row_bias(int64_t n, int d, const float* b, float* y, hipStream_t s);
+// The FCN readout (readout_as_fcn, FCN_e3nn nn/linear.py:94-129) of the fused
+// engine: a_0 = x, a_k = c f(a_{k-1} M_{k-1}) for the nh hidden layers, s =
+// a_nh . v, e = s * scale[t] + shift[t]; one launch writes eat[i] = e and
+// dx[i, :] = scale[t] ds/dx (what k_readout_bwd writes for the linear readout).
+// The packed weights (every matrix pre-scaled by 1 / sqrt(fan_in)): for k < nh
+// M_k [w[k]][stride(k)] row-major with an odd row stride >= w[k + 1] (padding
+// zero), then v [w[nh]]; padded to padded_floats().
+constexpr int FCN_MAX_HIDDEN = 4, FCN_MAX_WIDTH = 128;
+struct FcnDims {
+  int nh;                     // hidden layers: 1 .. FCN_MAX_HIDDEN
+  int w[FCN_MAX_HIDDEN + 1];  // w[0] = D (the row of x), w[1 .. nh] the hidden widths (1 .. FCN_MAX_WIDTH)
+  int kind;                   // activation f (fcn_act.h)
+  float c;                    // its normalize2mom constant (manifest readout.act_norm)
+  __host__ __device__ int stride(int k) const { return w[k + 1] | 1; }
+  __host__ __device__ int mat_off(int k) const {   // M_k (k < nh), v (k == nh)
+    int o = 0;
+    for (int q = 0; q < k; ++q) o += w[q] * stride(q);
+    return o;
+  }
+  __host__ __device__ int padded_floats() const { return (mat_off(nh) + w[nh] + 3) & ~3; }
+};
+hipError_t launch_readout_fcn(int n, const FcnDims& d, const float* x, const float* W, const int* type,
+                              const float* scale, const float* shift, float* eat, float* dx, hipStream_t s);
 int sum_blocks(int64_t n);
 hipError_t launch_sum(int64_t n, const float* a, float* part, float* out, hipStream_t s);
 hipError_t launch_final_sum(int nb, int k, const float* part, float* out, hipStream_t s);

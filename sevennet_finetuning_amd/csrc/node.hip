@@ -4,6 +4,7 @@
 // Every reduction here is deterministic: per-atom sums walk CSR lists in edge
 // order (no float atomics); scalar totals use a fixed two-level tree.
 #include "common.h"
+#include "fcn_act.h"
 
 #include <climits>
 #include "node.h"
@@ -683,6 +684,173 @@ __global__ void k_readout_bwd(int n, int D, const float* __restrict__ v, const i
   dx[idx] = scale[type[i]] * v[idx - i * D];
 }
 
+// use_bias_in_linear after the k_gemm fallback of a node linear: y[i, c] += b[c]
+__global__ void k_row_bias(int64_t n, int d, const float* __restrict__ b, float* __restrict__ y) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n * d) y[i] += b[i % d];
+}
+
+// The FCN readout with its backward, one pass per atom (node.h FcnDims for
+// the contract and the weight layout).  A wave owns FCN_AW = 8 atoms per pass,
+// four per half-wave: lane (h, l) = (lane / 32, lane % 32) owns unit l (+ 32,
+// 64, 96) of a layer for the atoms 4h .. 4h + 3.  The activations sit
+// interleaved in LDS (act[i * 8 + atom]: one b128 read, the same address
+// across a half-wave, feeds the four FMAs of a weight read), and every sum runs
+// over its inputs in ascending order, so the result is bitwise repeatable (no
+// atomics; the final dot product is a fixed butterfly over the half-wave).
+// Forward layer k stores c f'(z) per hidden unit; the backward overwrites it
+// in place with dE/dz (gz_k = (M_k gz_{k+1}) * c f'(z_k)) and the last step
+// writes dx = scale[t] * M_0 gz_1.  x is read once and dx written once.  The
+// odd row stride of the matrices makes both the forward's reads (lanes along a
+// row) and the backward's (lanes down a column) LDS-bank-conflict-free from
+// one copy.
+// LDSW: the packed weights staged in LDS once per workgroup (they fit beside
+// the scratch); otherwise read from global memory (L2) in the same layout.
+// LDS floats: [LDSW: padded_floats()] + waves x fcn_wave_floats().
+constexpr int FCN_AW = 8;
+__host__ __device__ inline int fcn_hmax(const FcnDims& d) {
+  int hmax = 0;
+  for (int k = 1; k <= d.nh; ++k) hmax = d.w[k] > hmax ? d.w[k] : hmax;
+  return hmax;
+}
+// per wave: x [8 D], two hidden activation buffers and nh derivative slots [8 hmax]
+__host__ __device__ inline int fcn_wave_floats(const FcnDims& d) {
+  return FCN_AW * (d.w[0] + (2 + d.nh) * fcn_hmax(d));
+}
+// sum over the 32 lanes of a half-wave, every lane gets the same bits
+__device__ __forceinline__ float half_wave_sum(float v) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <bool LDSW>
+__global__ __launch_bounds__(256) void k_readout_fcn(int n, FcnDims d, const float* __restrict__ x,
+                                                     const float* __restrict__ Wg,
+                                                     const int* __restrict__ type,
+                                                     const float* __restrict__ scale,
+                                                     const float* __restrict__ shift,
+                                                     float* __restrict__ eat, float* __restrict__ dx) {
+  extern __shared__ __attribute__((aligned(16))) float fcn_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = blockDim.x >> 6;
+  const int h4 = 4 * (lane >> 5), l = lane & 31;
+  const float* W = Wg;
+  float* scr = fcn_lds;
+  if constexpr (LDSW) {
+    const int nw = d.padded_floats();
+    for (int i = tid; i < nw; i += blockDim.x) fcn_lds[i] = Wg[i];
+    W = fcn_lds;
+    scr = fcn_lds + nw;
+  }
+  const int D = d.w[0], nh = d.nh, hmax = fcn_hmax(d);
+  float* xb = scr + wave * fcn_wave_floats(d);
+  float* hb0 = xb + FCN_AW * D;
+  float* hb1 = hb0 + FCN_AW * hmax;
+  float* dd = hb1 + FCN_AW * hmax;   // slot k: c f'(z) of hidden layer k + 1, then dE/dz
+  const float* wl = W + d.mat_off(nh);
+  __syncthreads();
+  // (the loop bound is the same for the whole workgroup: the barriers are legal)
+#pragma unroll 1
+  for (int base = blockIdx.x * nwave * FCN_AW; base < n; base += gridDim.x * nwave * FCN_AW) {
+    const int a0 = base + wave * FCN_AW;   // the wave's atoms a0 .. a0 + 7
+    for (int idx = lane; idx < FCN_AW * D; idx += 64) {
+      const int a = idx / D, i = idx - a * D;
+      xb[i * FCN_AW + a] = a0 + a < n ? x[(int64_t)a0 * D + idx] : 0.f;
+    }
+    __syncthreads();
+    const float* ain = xb;
+    float* aout = hb0;
+    float p[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int k = 0; k < nh; ++k) {
+      const int wi = d.w[k], wo = d.w[k + 1], ws = d.stride(k);
+      const float* M = W + d.mat_off(k);
+      float* dk = dd + k * FCN_AW * hmax;
+      const bool lastk = k == nh - 1;
+#pragma unroll 1
+      for (int jb = 0; jb < wo; jb += 32) {
+        const int j = jb + l < wo ? jb + l : wo - 1;   // (idle lanes repeat the last unit)
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+        for (int i = 0; i < wi; ++i) {
+          const float4 a = *reinterpret_cast<const float4*>(ain + FCN_AW * i + h4);
+          const float m = M[i * ws + j];
+          z[0] = fmaf(a.x, m, z[0]);
+          z[1] = fmaf(a.y, m, z[1]);
+          z[2] = fmaf(a.z, m, z[2]);
+          z[3] = fmaf(a.w, m, z[3]);
+        }
+        if (jb + l < wo) {
+          const float wj = lastk ? wl[j] : 0.f;
+          float av[4], dv[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            float f, df;
+            fcn_act(d.kind, z[q], f, df);
+            av[q] = d.c * f;
+            dv[q] = d.c * df;
+          }
+          if (lastk) {   // s = a_nh . v and dE/dz of the last hidden layer at once
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              p[q] = fmaf(av[q], wj, p[q]);
+              dv[q] *= wj;
+            }
+          } else {
+            *reinterpret_cast<float4*>(aout + FCN_AW * j + h4) = make_float4(av[0], av[1], av[2], av[3]);
+          }
+          *reinterpret_cast<float4*>(dk + FCN_AW * j + h4) = make_float4(dv[0], dv[1], dv[2], dv[3]);
+        }
+      }
+      __syncthreads();
+      ain = aout;
+      aout = aout == hb0 ? hb1 : hb0;
+    }
+    float sc[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      p[q] = half_wave_sum(p[q]);
+      const int a = a0 + h4 + q;
+      const int t = a < n ? type[a] : 0;
+      sc[q] = scale[t];
+      if (l == 0 && a < n) eat[a] = p[q] * sc[q] + shift[t];
+    }
+    // backward: dE/dz of hidden layer k from layer k + 1 through M_k, then dx through M_0
+#pragma unroll 1
+    for (int k = nh - 1; k >= 0; --k) {
+      const int wi = d.w[k], wo = d.w[k + 1], ws = d.stride(k);
+      const float* M = W + d.mat_off(k);
+      const float* gz = dd + k * FCN_AW * hmax;
+      float* dk = dd + (k > 0 ? k - 1 : 0) * FCN_AW * hmax;
+#pragma unroll 1
+      for (int ib = 0; ib < wi; ib += 32) {
+        const int i = ib + l < wi ? ib + l : wi - 1;
+        float g[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+        for (int j = 0; j < wo; ++j) {
+          const float4 gq = *reinterpret_cast<const float4*>(gz + FCN_AW * j + h4);
+          const float m = M[i * ws + j];
+          g[0] = fmaf(gq.x, m, g[0]);
+          g[1] = fmaf(gq.y, m, g[1]);
+          g[2] = fmaf(gq.z, m, g[2]);
+          g[3] = fmaf(gq.w, m, g[3]);
+        }
+        if (ib + l < wi) {
+          if (k > 0) {
+            float4* dp = reinterpret_cast<float4*>(dk + FCN_AW * i + h4);
+            const float4 dv = *dp;
+            *dp = make_float4(dv.x * g[0], dv.y * g[1], dv.z * g[2], dv.w * g[3]);
+          } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              if (a0 + h4 + q < n) dx[(int64_t)(a0 + h4 + q) * D + i] = sc[q] * g[q];
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 // per-block partial sums of a [n, stride] array's column `col` (fixed tree)
 __global__ void k_block_sum(int64_t n, const float* __restrict__ a, float* __restrict__ part) {
   __shared__ float red[TPB];
@@ -949,6 +1117,36 @@ hipError_t launch_readout(int n, int D, const float* x, const float* v, const in
 hipError_t launch_readout_bwd(int n, int D, const float* v, const int* type, const float* scale,
                               float* dx, hipStream_t s) {
   LAUNCH(k_readout_bwd, nblk((int64_t)n * D), n, D, v, type, scale, dx);
+  return hipGetLastError();
+}
+hipError_t launch_row_bias(int64_t n, int d, const float* b, float* y, hipStream_t s) {
+  LAUNCH(k_row_bias, nblk(n * d), n, d, b, y);
+  return hipGetLastError();
+}
+hipError_t launch_readout_fcn(int n, const FcnDims& d, const float* x, const float* W, const int* type,
+                              const float* scale, const float* shift, float* eat, float* dx, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (d.nh < 1 || d.nh > FCN_MAX_HIDDEN || d.w[0] < 1 || d.w[0] > FCN_MAX_WIDTH) return hipErrorInvalidValue;
+  for (int k = 1; k <= d.nh; ++k)
+    if (d.w[k] < 1 || d.w[k] > FCN_MAX_WIDTH) return hipErrorInvalidValue;
+  // the dynamic LDS of a launch: 64 KB.  Four waves with the weights staged
+  // when that fits; else the weights from global memory, and for the widest
+  // layers fewer waves per workgroup (8 x 128 x 7 floats per wave at most)
+  const size_t lim = 64 * 1024, wave = (size_t)fcn_wave_floats(d) * sizeof(float);
+  const size_t wbytes = (size_t)d.padded_floats() * sizeof(float);
+  const bool staged = wbytes + 4 * wave <= lim;
+  int nwave = 4;
+  while (!staged && nwave > 1 && nwave * wave > lim) nwave >>= 1;
+  const size_t lds = nwave * wave + (staged ? wbytes : 0);
+  if (lds > lim) return hipErrorInvalidValue;
+  const int per = nwave * FCN_AW;   // atoms per workgroup pass
+  const int grid = std::min((n + per - 1) / per, 2048);
+  if (staged)
+    hipLaunchKernelGGL(k_readout_fcn<true>, dim3(grid), dim3(64 * nwave), lds, s, n, d, x, W, type, scale,
+                       shift, eat, dx);
+  else
+    hipLaunchKernelGGL(k_readout_fcn<false>, dim3(grid), dim3(64 * nwave), lds, s, n, d, x, W, type, scale,
+                       shift, eat, dx);
   return hipGetLastError();
 }
 int sum_blocks(int64_t n) { return nblk(n); }

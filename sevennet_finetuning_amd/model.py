@@ -312,9 +312,10 @@ class GenericE3GNNModel:
 def load_model(model_dir=os.path.join(ASSETS, 'sevennet0'), device=None, engine='native'):
     """The engine for a deployment (pair_e3gnn.cpp:294-386 loads any deployed
     model): the native C-ABI engine (E3GNNModel -- SevenNet-0's specialised
-    kernels, or the generic engine of libe3gnn_hip.so for the rest of the
-    family); ``engine='torch'``: the trainable model in eval mode
-    (GenericE3GNNModel, autograd backward) for the non-SevenNet-0 ones."""
+    kernels, with or without linear biases and the FCN readout, or the
+    generic engine of libe3gnn_hip.so for the rest of the family);
+    ``engine='torch'``: the trainable model in eval mode (GenericE3GNNModel,
+    autograd backward) for the non-SevenNet-0 ones."""
     from .nn import sevennet0_kinds
     if engine not in ('native', 'torch'):
         raise ValueError(f"engine must be 'native' or 'torch', got {engine!r}")

@@ -291,7 +291,11 @@ def sevennet0_kinds(manifest, conv_only=False):
     same knobs): even-parity lmax-2 filters (SH of the unit vector, or of the
     raw vector for pre-0.9 checkpoints: one flag of the edge kernels), the
     XPLOR cutoff, a linear self-connection and exactly
-    128x0e -> 4 x (128x0e+64x1e+32x2e) -> 128x0e.  Returns the kernel kind of
+    128x0e -> 4 x (128x0e+64x1e+32x2e) -> 128x0e.  Linear biases
+    (``use_bias_in_linear``) and the FCN readout (``readout_as_fcn``, within
+    the readout kernel's limits: 1-4 hidden layers of 1-128 units) stay on the
+    same kernels: the biases ride in the node-linear epilogues and the FCN
+    readout has a kernel of its own.  Returns the kernel kind of
     every block (0 first, 1 middle, 2 last; csrc/tp.h) or None.
     ``conv_only``: only what the convolution kernels depend on (filter parity,
     lmax_edge, irreps) -- the trainable model computes the edge basis, SH and
@@ -301,9 +305,14 @@ def sevennet0_kinds(manifest, conv_only=False):
         return None
     cf = man.get('cutoff_function', {}) or {}
     if not conv_only and (man.get('self_connection_type', 'linear') != 'linear' or
-                          cf.get('name', 'XPLOR') != 'XPLOR' or bool(man.get('use_bias_in_linear')) or
-                          (man.get('readout') or {}).get('type', 'linear') != 'linear'):
+                          cf.get('name', 'XPLOR') != 'XPLOR'):
         return None
+    ro = man.get('readout') or {}
+    if not conv_only and ro.get('type', 'linear') != 'linear':
+        hidden = ro.get('hidden') or []
+        if ro.get('type') != 'fcn' or not 1 <= len(hidden) <= 4 or \
+                any(int(h) != h or not 1 <= h <= 128 for h in hidden):
+            return None
     irreps = [parse_irreps(s) for s in man['irreps_manual']]
     L = int(man['num_convolution_layer'])
     if len(irreps) != L + 1 or L < 2:
