@@ -22,6 +22,8 @@
  *   pack/unpack_{forward,reverse}_comm_gnn                          e3gnn_halo_pack/_unpack
  *     pair_e3gnn_parallel.cpp:803-933
  *   ASE primitive_neighbor_list / pair_e3gnn.cpp:144-182            e3gnn_nlist_*
+ *   the rank's graph per neighbour-list rebuild (owned, ghosts,     e3gnn_nlist_rank_build /
+ *     edges by local row) pair_e3gnn_parallel.cpp:258-314            _rank_fetch
  *   e3nn TensorProduct + message_gather under double backward       e3gnn_conv_graph /
  *     (training: convolution.py:104-123, trainer.py:155-222)         _forward / _backward
  *   e3nn normalize2mom(silu) and its derivatives (training)          e3gnn_act
@@ -459,6 +461,33 @@ int e3gnn_nlist_build(e3gnn_nlist* h, int64_t n, const double* pos, const double
                       const int* pbc, double cutoff, int64_t* n_edges, void* stream);
 int e3gnn_nlist_fetch(e3gnn_nlist* h, int32_t* edge_center, int32_t* edge_nbr, int32_t* shift,
                       float* edge_vec, void* stream);
+
+/* Rank graph of a spatial decomposition (pair_e3gnn_parallel.cpp:258-314), on
+ * the same handle: the graph parallel.build_rank_graph makes on the host,
+ * integer for integer.  owner: DEVICE int32 [n], values in [0, world) -- an
+ * input (the caller's bricks; the device does not recompute them); a value
+ * outside the range is reported as E3GNN_ERR_GRAPH.  All three dimensions are
+ * periodic (cell: HOST f64 [3][3], not NULL); world <= 256; at most 512
+ * neighbours per centre and shifts within +-1024 cells, as above.
+ *   rows [0, n_interior)        owned atoms with owned neighbours only, by id
+ *   rows [n_interior, n_local)  owned atoms with a neighbour of another rank, by id
+ *   rows [n_local, +n_ghost)    the distinct non-owned neighbours (one row per
+ *                               atom, whatever its images), by (owner, id)
+ *   edges                       every (i, j, S) with i owned, sorted by (row of
+ *                               i, global id of j, S); center / nbr are rows
+ * e3gnn_nlist_rank_build counts the rows and edges (synchronises `stream`) and
+ * keeps the row maps.  e3gnn_nlist_rank_fetch writes device outputs sized from
+ * the counts: owned [n_local] and ghosts [n_ghost] (global ids), recv_counts
+ * [world] int64 (ghosts per owner), edge_center / edge_nbr [E] (local rows),
+ * shift [E][3], edge_vec [E][3] (shift, edge_vec nullable).  Every output is
+ * bitwise reproducible.  Either build invalidates the other's fetch. */
+int e3gnn_nlist_rank_build(e3gnn_nlist* h, int64_t n, const double* pos, const double* cell,
+                           double cutoff, const int32_t* owner, int rank, int world,
+                           int64_t* n_local, int64_t* n_interior, int64_t* n_ghost,
+                           int64_t* n_edges, void* stream);
+int e3gnn_nlist_rank_fetch(e3gnn_nlist* h, int32_t* owned, int32_t* ghosts, int64_t* recv_counts,
+                           int32_t* edge_center, int32_t* edge_nbr, int32_t* shift,
+                           float* edge_vec, void* stream);
 
 /* ---- DFT-D3 dispersion ----
  * Replaces the reference's LAMMPS pair style d3 (sevenn/pair_e3gnn/pair_d3.cu):

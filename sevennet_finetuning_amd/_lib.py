@@ -94,6 +94,10 @@ SIGNATURES = {
     'e3gnn_nlist_build': (_c_int, [_vp, _c_i64, _vp, _P(ctypes.c_double), _P(_c_int),
                                    ctypes.c_double, _P(_c_i64), _vp]),
     'e3gnn_nlist_fetch': (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    'e3gnn_nlist_rank_build': (_c_int, [_vp, _c_i64, _vp, _P(ctypes.c_double), ctypes.c_double,
+                                        _vp, _c_int, _c_int, _P(_c_i64), _P(_c_i64), _P(_c_i64),
+                                        _P(_c_i64), _vp]),
+    'e3gnn_nlist_rank_fetch': (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'e3gnn_set_impl': (_c_int, [_vp, _c_int]),
     'e3gnn_set_timing': (_c_int, [_vp, _c_int]),
     'e3gnn_set_stream_ordered': (_c_int, [_vp, _c_int]),

@@ -107,24 +107,30 @@ __device__ __forceinline__ Hit nl_vec(const double* __restrict__ pos, const NlGe
   return h;
 }
 
-// one wave per centre; FILL = false: count, true: collect, sort, write
-template <bool FILL>
+// one wave per centre; FILL = false: count, true: collect, sort, write.
+// RANK = true is the rank-graph form (NlRank): the n centres are a list of atom
+// ids, the count pass also flags boundary centres and ghost atoms, and the fill
+// pass writes local rows (the centre's position in the list, lid[j]) while the
+// keys still sort by the global (j, S).
+template <bool FILL, bool RANK>
 __global__ __launch_bounds__(256) void k_nl_search(
     int n, const double* __restrict__ pos, NlGeom G, const int* __restrict__ f0,
     const int* __restrict__ bin, const int* __restrict__ bin_start,
     const int* __restrict__ bin_atoms, int* __restrict__ deg, const int* __restrict__ row_ptr,
     int* __restrict__ center, int* __restrict__ nbr, int* __restrict__ shift,
-    float* __restrict__ vec, int* __restrict__ err) {
+    float* __restrict__ vec, int* __restrict__ err, NlRank rk) {
   __shared__ unsigned long long keys[4][NL_MAXD];
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wid);
-  if (i >= n) return;
+  const int ci = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wid);
+  if (ci >= n) return;
+  const int i = RANK ? __builtin_amdgcn_readfirstlane(rk.centers[ci]) : ci;
   unsigned long long* K = keys[wid];
   const int bi = bin[i];
   const int b[3] = {bi / (G.nb[1] * G.nb[2]), (bi / G.nb[2]) % G.nb[1], bi % G.nb[2]};
   const int fi[3] = {f0[3 * i], f0[3 * i + 1], f0[3 * i + 2]};
   const double rc2 = G.rc2;
   int count = 0;  // uniform
+  bool boundary = false;  // uniform (RANK count pass)
   for (int ox = -G.R[0]; ox <= G.R[0]; ++ox)
     for (int oy = -G.R[1]; oy <= G.R[1]; ++oy)
       for (int oz = -G.R[2]; oz <= G.R[2]; ++oz) {
@@ -159,6 +165,12 @@ __global__ __launch_bounds__(256) void k_nl_search(
             hit = r2 < rc2 && !(j == i && S[0] == 0 && S[1] == 0 && S[2] == 0);
           }
           const unsigned long long m = __ballot(hit);
+          if constexpr (RANK && !FILL) {
+            // same-value stores: the flags do not depend on the order of arrival
+            const bool foreign = hit && rk.owner[j] != rk.rank;
+            if (foreign) rk.ghost_flag[j] = 1;
+            boundary |= __ballot(foreign) != 0;
+          }
           if (FILL && hit) {
             const int slot = count + __popcll(m & ((1ull << lane) - 1));
             const int lim = 1 << SB;
@@ -173,7 +185,8 @@ __global__ __launch_bounds__(256) void k_nl_search(
       }
   if constexpr (!FILL) {
     if (lane == 0) {
-      deg[i] = count;
+      deg[ci] = count;
+      if constexpr (RANK) rk.boundary_flag[ci] = boundary ? 1 : 0;
       if (count > NL_MAXD) atomicOr(err, 4);
     }
     return;
@@ -201,7 +214,7 @@ __global__ __launch_bounds__(256) void k_nl_search(
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       }
-    const int base = row_ptr[i];
+    const int base = row_ptr[ci];
     for (int t = lane; t < count; t += 64) {
       const unsigned long long key = K[t];
       const int j = (int)(key >> 33);
@@ -210,8 +223,8 @@ __global__ __launch_bounds__(256) void k_nl_search(
       const int sz = (int)(key & 0x7ff) - (1 << SB);
       const Hit h = nl_vec(pos, G, i, j, sx, sy, sz);
       const int64_t q = (int64_t)base + t;
-      center[q] = i;
-      nbr[q] = j;
+      center[q] = ci;
+      nbr[q] = RANK ? rk.lid[j] : j;
       if (shift) {
         shift[3 * q] = sx;
         shift[3 * q + 1] = sy;
@@ -224,6 +237,142 @@ __global__ __launch_bounds__(256) void k_nl_search(
       }
     }
   }
+}
+
+// ---------------------------------------------------------------- rank graph
+// Row order of one rank of a spatial decomposition (parallel.py RankGraph):
+// owned atoms interior-first then boundary, each by id; ghosts by (owner, id).
+// Every position below comes from a scan or a ballot, never from the order in
+// which threads arrive, so the outputs are bitwise reproducible.
+
+// Exclusive scan over many workgroups (the per-atom arrays of the rank graph:
+// k_nl_scan is one workgroup, 2 ms at 778k entries).  Blocks of 1024 entries,
+// four consecutive ones per thread: FINAL = false writes each block's sum,
+// k_nl_scan turns the sums into block offsets (boff, boff[nblk] = total),
+// FINAL = true rescans its block and writes out[0..n] (out[n] = total).
+constexpr int SCAN_BLK = 1024;
+template <bool FINAL>
+__global__ __launch_bounds__(256) void k_rk_scan(int n, const int* __restrict__ cnt,
+                                                 int* __restrict__ bsum,
+                                                 const int* __restrict__ boff,
+                                                 int* __restrict__ out) {
+  __shared__ int part[256];
+  const int t = threadIdx.x;
+  const int base = blockIdx.x * SCAN_BLK + 4 * t;
+  int v[4], s = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    v[k] = base + k < n ? cnt[base + k] : 0;
+    s += v[k];
+  }
+  part[t] = s;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {  // Hillis-Steele inclusive scan
+    const int u = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += u;
+    __syncthreads();
+  }
+  if constexpr (!FINAL) {
+    if (t == 255) bsum[blockIdx.x] = part[255];
+  } else {
+    int run = boff[blockIdx.x] + (part[t] - s);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (base + k < n) out[base + k] = run;
+      run += v[k];
+    }
+    if (blockIdx.x == gridDim.x - 1 && t == 255) out[n] = boff[gridDim.x];
+  }
+}
+
+// mine[a] = 1 for the rank's atoms; owner values outside [0, world) -> err bit 8
+__global__ void k_rk_mark(int n, const int* __restrict__ owner, int rank, int world,
+                          int* __restrict__ mine, int* __restrict__ err) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= n) return;
+  const int o = owner[a];
+  if (o < 0 || o >= world) atomicOr(err, 8);
+  mine[a] = o == rank ? 1 : 0;
+}
+
+// out[pos[a]] = a for every flagged a (pos = exclusive scan of flag): ascending ids
+__global__ void k_rk_compact(int n, const int* __restrict__ flag, const int* __restrict__ pos,
+                             int* __restrict__ out) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= n) return;
+  if (flag[a]) out[pos[a]] = a;
+}
+
+// centre c of the id-ordered list -> its local row (bpos = exclusive scan of the
+// boundary flags, bpos[nc] = number of boundary centres); owned, the degrees in
+// row order and lid of the owned atoms
+__global__ void k_rk_rows(int nc, const int* __restrict__ centers, const int* __restrict__ bflag,
+                          const int* __restrict__ bpos, const int* __restrict__ deg,
+                          int* __restrict__ owned, int* __restrict__ deg_row,
+                          int* __restrict__ lid) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const int n_interior = nc - bpos[nc];
+  const int r = bflag[c] ? n_interior + bpos[c] : c - bpos[c];
+  const int a = centers[c];
+  owned[r] = a;
+  deg_row[r] = deg[c];
+  lid[a] = r;
+}
+
+// Stable counting sort of the id-ordered ghost list by owner, blocks of 256
+// ghosts.  A ghost's place inside its block among those of the same owner:
+// its lane's rank in the wave's ballot of that owner plus the counts of the
+// block's earlier waves.  SCATTER = false writes the per-block histogram
+// hist[o * nblk + b]; after its exclusive scan (off), SCATTER = true places
+// the ghosts and completes lid.
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void k_rk_ghost_sort(
+    int ng, int world, int nblk, const int* __restrict__ gid, const int* __restrict__ owner,
+    int* __restrict__ hist, const int* __restrict__ off, int n_local, int* __restrict__ ghosts,
+    int* __restrict__ lid) {
+  __shared__ int cnt[4][NL_MAX_WORLD];
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int t = threadIdx.x; t < 4 * NL_MAX_WORLD; t += 256) (&cnt[0][0])[t] = 0;
+  __syncthreads();
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  const bool live = g < ng;
+  const int a = live ? gid[g] : 0;
+  const int o = live ? owner[a] : -1;
+  int in_wave = 0;
+  bool todo = live;
+  while (__ballot(todo)) {  // one round per distinct owner in the wave
+    const unsigned long long act = __ballot(todo);
+    const int lead = __ffsll((long long)act) - 1;
+    const int v = __shfl(o, lead);
+    const unsigned long long m = __ballot(todo && o == v);
+    if (todo && o == v) {
+      in_wave = __popcll(m & ((1ull << lane) - 1));
+      if (lane == lead) cnt[wid][v] = __popcll(m);
+      todo = false;
+    }
+  }
+  __syncthreads();
+  if constexpr (!SCATTER) {
+    if ((int)threadIdx.x < world)
+      hist[threadIdx.x * nblk + blockIdx.x] = ((cnt[0][threadIdx.x] + cnt[1][threadIdx.x]) +
+                                               cnt[2][threadIdx.x]) + cnt[3][threadIdx.x];
+  } else if (live) {
+    int before = in_wave;
+    for (int w = 0; w < wid; ++w) before += cnt[w][o];
+    const int q = off[o * nblk + blockIdx.x] + before;
+    ghosts[q] = a;
+    lid[a] = n_local + q;
+  }
+}
+
+// recv_counts[o] = ghosts of owner o, from the scanned histogram
+__global__ void k_rk_recv(int world, int nblk, const int* __restrict__ off,
+                          long long* __restrict__ recv_counts) {
+  const int o = blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= world) return;
+  recv_counts[o] = (long long)off[(o + 1) * nblk] - off[o * nblk];
 }
 
 }  // namespace
@@ -253,11 +402,73 @@ hipError_t launch_nl_search(bool fill, int n, const double* pos, const NlGeom& G
   if (n <= 0) return hipSuccess;
   const dim3 grid((n + 3) / 4), block(256);
   if (fill)
-    hipLaunchKernelGGL(k_nl_search<true>, grid, block, 0, s, n, pos, G, f0, bin, bin_start,
-                       bin_atoms, deg, row_ptr, center, nbr, shift, vec, err);
+    hipLaunchKernelGGL((k_nl_search<true, false>), grid, block, 0, s, n, pos, G, f0, bin,
+                       bin_start, bin_atoms, deg, row_ptr, center, nbr, shift, vec, err, NlRank{});
   else
-    hipLaunchKernelGGL(k_nl_search<false>, grid, block, 0, s, n, pos, G, f0, bin, bin_start,
-                       bin_atoms, deg, row_ptr, center, nbr, shift, vec, err);
+    hipLaunchKernelGGL((k_nl_search<false, false>), grid, block, 0, s, n, pos, G, f0, bin,
+                       bin_start, bin_atoms, deg, row_ptr, center, nbr, shift, vec, err, NlRank{});
+  return hipGetLastError();
+}
+hipError_t launch_nl_rank_search(bool fill, int nc, const double* pos, const NlGeom& G,
+                                 const int* f0, const int* bin, const int* bin_start,
+                                 const int* bin_atoms, int* deg, const int* row_ptr, int* center,
+                                 int* nbr, int* shift, float* vec, int* err, const NlRank& rk,
+                                 hipStream_t s) {
+  if (nc <= 0) return hipSuccess;
+  const dim3 grid((nc + 3) / 4), block(256);
+  if (fill)
+    hipLaunchKernelGGL((k_nl_search<true, true>), grid, block, 0, s, nc, pos, G, f0, bin,
+                       bin_start, bin_atoms, deg, row_ptr, center, nbr, shift, vec, err, rk);
+  else
+    hipLaunchKernelGGL((k_nl_search<false, true>), grid, block, 0, s, nc, pos, G, f0, bin,
+                       bin_start, bin_atoms, deg, row_ptr, center, nbr, shift, vec, err, rk);
+  return hipGetLastError();
+}
+int nl_scan_blocks(int n) { return n > 0 ? (n + SCAN_BLK - 1) / SCAN_BLK : 1; }
+hipError_t launch_rk_scan(int n, const int* cnt, int* out, int* bsum, int* boff, hipStream_t s) {
+  const int nblk = nl_scan_blocks(n);
+  hipLaunchKernelGGL(k_rk_scan<false>, dim3(nblk), dim3(256), 0, s, n, cnt, bsum, nullptr,
+                     nullptr);
+  hipLaunchKernelGGL(k_nl_scan, dim3(1), dim3(1024), 0, s, nblk, bsum, boff);
+  hipLaunchKernelGGL(k_rk_scan<true>, dim3(nblk), dim3(256), 0, s, n, cnt, nullptr, boff, out);
+  return hipGetLastError();
+}
+hipError_t launch_rk_mark(int n, const int* owner, int rank, int world, int* mine, int* err,
+                          hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rk_mark, dim3((n + 255) / 256), dim3(256), 0, s, n, owner, rank, world,
+                     mine, err);
+  return hipGetLastError();
+}
+hipError_t launch_rk_compact(int n, const int* flag, const int* pos, int* out, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rk_compact, dim3((n + 255) / 256), dim3(256), 0, s, n, flag, pos, out);
+  return hipGetLastError();
+}
+hipError_t launch_rk_rows(int nc, const int* centers, const int* bflag, const int* bpos,
+                          const int* deg, int* owned, int* deg_row, int* lid, hipStream_t s) {
+  if (nc <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rk_rows, dim3((nc + 255) / 256), dim3(256), 0, s, nc, centers, bflag, bpos,
+                     deg, owned, deg_row, lid);
+  return hipGetLastError();
+}
+hipError_t launch_rk_ghost_sort(bool scatter, int ng, int world, int nblk, const int* gid,
+                                const int* owner, int* hist, const int* off, int n_local,
+                                int* ghosts, int* lid, hipStream_t s) {
+  if (world < 1 || world > NL_MAX_WORLD || nblk < 1 || (int64_t)nblk * 256 < ng)
+    return hipErrorInvalidValue;
+  if (scatter)
+    hipLaunchKernelGGL(k_rk_ghost_sort<true>, dim3(nblk), dim3(256), 0, s, ng, world, nblk, gid,
+                       owner, hist, off, n_local, ghosts, lid);
+  else
+    hipLaunchKernelGGL(k_rk_ghost_sort<false>, dim3(nblk), dim3(256), 0, s, ng, world, nblk, gid,
+                       owner, hist, off, n_local, ghosts, lid);
+  return hipGetLastError();
+}
+hipError_t launch_rk_recv(int world, int nblk, const int* off, int64_t* recv_counts,
+                          hipStream_t s) {
+  hipLaunchKernelGGL(k_rk_recv, dim3((world + 63) / 64), dim3(64), 0, s, world, nblk, off,
+                     (long long*)recv_counts);
   return hipGetLastError();
 }
 

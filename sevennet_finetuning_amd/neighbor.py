@@ -117,7 +117,11 @@ class DeviceNeighborList:
     ``(edge_center int32 [E], edge_nbr int32 [E], shift int32 [E, 3],
     edge_vec float32 [E, 3])``.  pbc must be all True or all False (the
     device list raises ``E3GNNError`` otherwise; ``neighbor_list`` covers the
-    mixed case on the host)."""
+    mixed case on the host).
+
+    ``rank_graph(pos, cell, cutoff, owner, rank, world)`` builds one rank's
+    graph of a spatial decomposition on the same handle (see there and
+    ``parallel.build_rank_graph_device``)."""
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -156,3 +160,49 @@ class DeviceNeighborList:
         L.check(self.lib.e3gnn_nlist_fetch(self._h, center.data_ptr(), nbr.data_ptr(),
                                            shift.data_ptr(), vec.data_ptr(), s))
         return center, nbr, shift, vec
+
+    def rank_graph(self, pos, cell, cutoff, owner, rank, world, pbc=(True, True, True)):
+        """One rank's graph of a spatial decomposition, built on the device
+        (``e3gnn_nlist_rank_*``): the rows, ghosts and edges of
+        ``parallel.build_rank_graph``, integer for integer.
+
+        ``owner``: int32 [n] owner rank of every atom, an input (the device
+        does not recompute the bricks).  Returns a dict of device tensors
+        ``owned`` int32 [n_local] and ``ghosts`` int32 [n_ghost] (global ids;
+        interior rows first, ghosts by (owner, id)), ``recv_counts`` int64
+        [world], ``center`` / ``nbr`` int32 [E] (local rows), ``shift`` int32
+        [E, 3], ``vec`` float32 [E, 3], and the host integers ``n_local``,
+        ``n_interior``, ``n_ghost``.
+
+        Limits: all three dimensions periodic (anything else raises
+        ``E3GNNError``; the host builder serves those cases), at most 512
+        neighbours per centre (``NL_MAXD``), shifts within +-1024 cells,
+        ``world`` <= 256.  The outputs are bitwise reproducible."""
+        import ctypes
+        torch, L = self._torch, self._L
+        dev = self.device
+        if not all(bool(p) for p in pbc):
+            raise L.E3GNNError('e3gnn error 1: device rank graph: all three dimensions must be '
+                               'periodic (parallel.build_rank_graph covers the rest on the host)')
+        pos = torch.as_tensor(pos).to(dev, torch.float64).contiguous()
+        n = int(pos.shape[0])
+        owner = torch.as_tensor(owner).to(dev, torch.int32).contiguous()
+        if owner.shape != (n,):
+            raise ValueError('owner must have one entry per atom')
+        cellh = (ctypes.c_double * 9)(*np.asarray(cell, dtype=np.float64).reshape(-1).tolist())
+        cnt = [ctypes.c_int64() for _ in range(4)]
+        s = torch.cuda.current_stream(dev).cuda_stream
+        L.check(self.lib.e3gnn_nlist_rank_build(self._h, n, pos.data_ptr(), cellh, float(cutoff),
+                                                owner.data_ptr(), int(rank), int(world),
+                                                *[ctypes.byref(c) for c in cnt], s))
+        nl, ni, ng, E = (c.value for c in cnt)
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)  # noqa: E731
+        out = {'owned': i32(nl), 'ghosts': i32(ng),
+               'recv_counts': torch.empty(int(world), dtype=torch.int64, device=dev),
+               'center': i32(E), 'nbr': i32(E), 'shift': i32(E, 3),
+               'vec': torch.empty(E, 3, dtype=torch.float32, device=dev)}
+        L.check(self.lib.e3gnn_nlist_rank_fetch(
+            self._h, *[out[k].data_ptr() for k in ('owned', 'ghosts', 'recv_counts', 'center',
+                                                   'nbr', 'shift', 'vec')], s))
+        out.update(n_local=nl, n_interior=ni, n_ghost=ng)
+        return out

@@ -21,6 +21,14 @@ Here, one process per GPU:
   enters the edge vector), ordered by (owner rank, id) so each peer's ghosts
   are one contiguous block.  A one-time handshake (all_to_all) tells every
   owner which of its rows each peer needs.
+* ``build_rank_graph_device`` builds the same graph on the GPU
+  (csrc/neighbor.hip, ``e3gnn_nlist_rank_*``) as a ``DeviceRankGraph``, equal
+  to the host graph integer for integer; ``handshake``, ``Halo``,
+  ``HipSegmentEngine.upload`` and ``ParallelE3GNN.set_graph`` take either.
+  The owner of every atom is an input to the device (``owners`` runs on the
+  host, so both builders split the atoms by the same arithmetic).  Limits:
+  all-periodic cells, 512 neighbours per centre, world <= 256; the host
+  builder serves everything else.
 * ``Halo`` moves rows with one ``all_to_all_single`` per exchange (RCCL over
   xGMI with backend "nccl"; host-staged with "gloo"), packing and unpacking
   with the library's halo kernels.  Reverse exchanges accumulate per peer
@@ -140,9 +148,141 @@ def build_rank_graph(pos, cell, types, cutoff, grid, rank, pbc=(True, True, True
         req_ids=ghosts.astype(np.int64), n_interior=n_interior)
 
 
+@dataclass
+class DeviceRankGraph:
+    """A ``RankGraph`` whose arrays are tensors of the engine's device (built
+    there by ``build_rank_graph_device``): the engine takes ``types``,
+    ``center``, ``nbr`` and ``vec`` in place, nothing large goes through the
+    host.  The row counts and ``recv_counts`` are also held on the host (the
+    split sizes of the exchanges have to be)."""
+    rank: int
+    world: int
+    grid: tuple
+    owned: torch.Tensor          # int32 [n_local] global ids, interior rows first
+    ghosts: torch.Tensor         # int32 [n_ghost] global ids, by (owner, id)
+    types: torch.Tensor          # int32 [n_local + n_ghost]
+    center: torch.Tensor         # int32 [E] local rows (sorted)
+    nbr: torch.Tensor            # int32 [E] local rows
+    vec: torch.Tensor            # float32 [E, 3]
+    recv_counts: torch.Tensor    # int64 [world]
+    recv_rows: torch.Tensor      # int64 [n_ghost]
+    req_ids: torch.Tensor        # int64 [n_ghost]
+    n_local: int = 0
+    n_ghost: int = 0
+    n_interior: int = 0
+    recv_counts_host: np.ndarray = field(default=None)   # int64 [world]
+    shift: torch.Tensor = field(default=None)            # int32 [E, 3] (device builds)
+    send_counts: np.ndarray = field(default=None)        # host int64 [world]
+    send_rows: torch.Tensor = field(default=None)        # int64, our local rows by peer
+
+    def to_host(self):
+        """The same graph as a ``RankGraph`` of numpy arrays (``vec`` float32)."""
+        h = lambda t, dt: t.detach().cpu().numpy().astype(dt)  # noqa: E731
+        return RankGraph(
+            rank=self.rank, world=self.world, grid=tuple(self.grid),
+            owned=h(self.owned, np.int64), ghosts=h(self.ghosts, np.int64),
+            types=h(self.types, np.int32), center=h(self.center, np.int32),
+            nbr=h(self.nbr, np.int32), vec=h(self.vec, np.float32),
+            recv_counts=h(self.recv_counts, np.int64), recv_rows=h(self.recv_rows, np.int64),
+            req_ids=h(self.req_ids, np.int64), n_interior=int(self.n_interior),
+            send_counts=None if self.send_counts is None else
+            np.asarray(self.send_counts, dtype=np.int64),
+            send_rows=None if self.send_rows is None else h(self.send_rows, np.int64))
+
+    @classmethod
+    def from_host(cls, rg, device):
+        """A host ``RankGraph`` moved to ``device`` (``vec`` cast to float32)."""
+        t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), device=device).to(dt)  # noqa: E731
+        return cls(
+            rank=rg.rank, world=rg.world, grid=tuple(rg.grid),
+            owned=t(rg.owned, torch.int32), ghosts=t(rg.ghosts, torch.int32),
+            types=t(rg.types, torch.int32), center=t(rg.center, torch.int32),
+            nbr=t(rg.nbr, torch.int32),
+            vec=t(np.asarray(rg.vec, dtype=np.float32).reshape(-1, 3), torch.float32),
+            recv_counts=t(rg.recv_counts, torch.int64), recv_rows=t(rg.recv_rows, torch.int64),
+            req_ids=t(rg.req_ids, torch.int64), n_local=int(rg.n_local), n_ghost=int(rg.n_ghost),
+            n_interior=int(rg.n_interior),
+            recv_counts_host=np.asarray(rg.recv_counts, dtype=np.int64).copy(),
+            send_counts=None if rg.send_counts is None else
+            np.asarray(rg.send_counts, dtype=np.int64).copy(),
+            send_rows=None if rg.send_rows is None else t(rg.send_rows, torch.int64))
+
+
+def build_rank_graph_device(pos, cell, types, cutoff, grid, rank, device, nlist=None,
+                            pbc=(True, True, True)):
+    """``build_rank_graph`` on the GPU (``e3gnn_nlist_rank_*``, csrc/neighbor.hip):
+    the same rows, ghosts, edges and order, integer for integer, as a
+    ``DeviceRankGraph`` of ``device``.
+
+    Ownership is an input of the device builder: ``owners`` runs here on the
+    host (O(n) numpy) and the int32 array is uploaded, so both builders split
+    the atoms by the same arithmetic.  ``nlist``: a ``DeviceNeighborList`` of
+    ``device`` to reuse (its workspaces grow once), else one is created.
+
+    Limits: all three dimensions periodic (``E3GNNError`` otherwise; the host
+    builder serves mixed and open boundaries), at most 512 neighbours per
+    centre (``NL_MAXD``), image shifts within +-1024 cells, ``world`` <= 256."""
+    from .neighbor import DeviceNeighborList
+    if not all(bool(p) for p in pbc):
+        raise _lib.E3GNNError('e3gnn error 1: device rank graph: all three dimensions must be '
+                              'periodic (build_rank_graph covers the rest on the host)')
+    world = int(np.prod(grid))
+    if nlist is None:
+        nlist = DeviceNeighborList(device)
+    dev = nlist.device
+    pos_h = pos.detach().cpu().numpy() if torch.is_tensor(pos) else pos
+    own = torch.as_tensor(owners(pos_h, cell, grid).astype(np.int32), device=dev)
+    g = nlist.rank_graph(pos, cell, cutoff, own, rank, world)
+    nl, ng = g['n_local'], g['n_ghost']
+    types = torch.as_tensor(np.asarray(types) if not torch.is_tensor(types) else types,
+                            device=dev).to(torch.int32)
+    rows = torch.cat([g['owned'], g['ghosts']]).to(torch.int64)
+    return DeviceRankGraph(
+        rank=int(rank), world=world, grid=tuple(grid), owned=g['owned'], ghosts=g['ghosts'],
+        types=types[rows].contiguous(), center=g['center'], nbr=g['nbr'], vec=g['vec'],
+        recv_counts=g['recv_counts'],
+        recv_rows=nl + torch.arange(ng, dtype=torch.int64, device=dev),
+        req_ids=g['ghosts'].to(torch.int64), n_local=nl, n_ghost=ng,
+        n_interior=g['n_interior'], recv_counts_host=g['recv_counts'].cpu().numpy(),
+        shift=g['shift'])
+
+
+def _handshake_device(rg, group, device):
+    """``handshake`` of a ``DeviceRankGraph``: the id lists are small and go
+    through the host (with "gloo" they have to); the send rows end up on the
+    graph's device."""
+    w = rg.world
+    dev = rg.owned.device
+    if w == 1:
+        rg.send_counts = np.zeros(1, dtype=np.int64)
+        rg.send_rows = torch.zeros(0, dtype=torch.int64, device=dev)
+        return rg
+    rc = torch.as_tensor(rg.recv_counts_host, dtype=torch.int64, device=device)
+    sc = torch.empty_like(rc)
+    dist.all_to_all_single(sc, rc, group=group)
+    send_counts = sc.cpu().numpy()
+    req = rg.req_ids.to(device)
+    ids = torch.empty(int(send_counts.sum()), dtype=torch.int64, device=device)
+    dist.all_to_all_single(ids, req, output_split_sizes=send_counts.tolist(),
+                           input_split_sizes=rg.recv_counts_host.tolist(), group=group)
+    ids = ids.cpu().numpy()
+    owned = rg.owned.cpu().numpy().astype(np.int64)
+    srt = np.argsort(owned)
+    rows = srt[np.searchsorted(owned, ids, sorter=srt)].astype(np.int64) if len(ids) else \
+        np.zeros(0, dtype=np.int64)
+    if len(ids) and not np.array_equal(owned[rows], ids):
+        raise RuntimeError('halo handshake: a peer asked for an atom this rank does not own')
+    rg.send_counts = send_counts
+    rg.send_rows = torch.as_tensor(rows, device=dev)
+    return rg
+
+
 def handshake(rg, group=None, device='cpu'):
     """Tell every owner which of its atoms we need (global ids, one-time per
-    graph); the owner turns them into its local rows."""
+    graph); the owner turns them into its local rows.  Host and device graphs
+    (``RankGraph``, ``DeviceRankGraph``) are both served."""
+    if isinstance(rg, DeviceRankGraph):
+        return _handshake_device(rg, group, device)
     w = rg.world
     if w == 1:
         rg.send_counts = np.zeros(1, dtype=np.int64)
@@ -204,11 +344,16 @@ class Halo:
         dev = engine.device
         self.staged = dist.is_initialized() and dist.get_backend(group) == 'gloo' \
             and torch.device(dev).type != 'cpu'
-        i32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.int32), device=dev)
-        self.send_rows = i32(rg.send_rows)
-        self.recv_rows = i32(rg.recv_rows)
+        if isinstance(rg, DeviceRankGraph):   # index lists already on the device
+            self.send_rows = rg.send_rows.to(dev, torch.int32)
+            self.recv_rows = rg.recv_rows.to(dev, torch.int32)
+            self.rc = [int(x) for x in rg.recv_counts_host]
+        else:
+            i32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.int32), device=dev)
+            self.send_rows = i32(rg.send_rows)
+            self.recv_rows = i32(rg.recv_rows)
+            self.rc = [int(x) for x in rg.recv_counts]
         self.sc = [int(x) for x in rg.send_counts]
-        self.rc = [int(x) for x in rg.recv_counts]
         self.soff = np.concatenate([[0], np.cumsum(self.sc)]).astype(np.int64)
 
     def _a2a_start(self, out, inp, out_splits, in_splits):
@@ -349,12 +494,19 @@ class HipSegmentEngine:
         (the reference rebuilds its graph tensors per LAMMPS neighbour list,
         pair_e3gnn_parallel.cpp:258-314), so a step moves no host data."""
         dev = self.device
-        t32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.int32), device=dev)
         self.n = rg.n_local + rg.n_ghost
         self.nl = rg.n_local
         self.n_ghost = rg.n_ghost
-        self._in = (t32(rg.types), t32(rg.center), t32(rg.nbr),
-                    torch.as_tensor(np.asarray(rg.vec, dtype=np.float32), device=dev))
+        if isinstance(rg, DeviceRankGraph):
+            # built on the device: the tensors are used in place (.to of a
+            # matching contiguous tensor returns the tensor itself)
+            d32 = lambda a: a.to(dev, torch.int32).contiguous()
+            self._in = (d32(rg.types), d32(rg.center), d32(rg.nbr),
+                        rg.vec.to(dev, torch.float32).contiguous())
+        else:
+            t32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.int32), device=dev)
+            self._in = (t32(rg.types), t32(rg.center), t32(rg.nbr),
+                        torch.as_tensor(np.asarray(rg.vec, dtype=np.float32), device=dev))
         _lib.check(self.lib.e3gnn_set_interior(self.ctx, int(rg.n_interior)))
 
     def graph_set(self):
