@@ -88,6 +88,110 @@ __device__ __forceinline__ void sum_rows4_n(float (&v)[N]) {
   for (int i = 0; i < N; ++i) v[i] = a[i] + b[i];
 }
 
+// the same sums as a reduce-scatter: N different values need no N all-reduces
+// when one row is to store each total.  Stage 1 swaps value q against value
+// q + 2 (v_permlane32_swap: the upper 32 lanes of the first operand <-> the
+// lower 32 of the second), so one swap + one add leave q's half sums r0 + r2
+// (even row) and r1 + r3 (odd row) in lanes 0-31 and (q + 2)'s in lanes 32-63;
+// stage 2 swaps the (0, 2) result against the (1, 3) result
+// (v_permlane16_swap: the odd rows of the first <-> the even rows of the
+// second) and adds.  Every total is (r0 + r2) + (r1 + r3), the pairs
+// sum_rows4 adds: the same bits, only the lane holding them differs.
+// Who holds what afterwards (row = lane >> 4):
+//   N = 4: out[0] of row g is the total of v[g]               (3 swaps, 3 adds)
+//   N = 3: rows 0, 1, 2 hold v[0], v[1], v[2]; row 3 v[1] again (same bits)
+//   N = 2: rows 0 and 1 hold v[0], rows 2 and 3 hold v[1]     (2 swaps, 2 adds)
+//   N = 1: every row holds v[0] (the all-reduce)
+//   N = 5: out[0] as N = 4 for v[0..3], out[1] as N = 1 for v[4], the five
+//          swaps in the same two hazard-padded groups         (5 swaps, 5 adds)
+template <int N>
+__device__ __forceinline__ void sum_rows4_scatter(const float (&v)[N], float (&out)[(N + 3) / 4]) {
+  static_assert(N >= 1 && N <= 5, "up to five values per group");
+  if constexpr (N <= 2) {
+    float a[1] = {v[0]}, b[1] = {v[N - 1]};
+    permlane_swap_n32<1>(a, b);
+    float s[1] = {a[0] + b[0]};
+    float t[1] = {s[0]};
+    permlane_swap_n16<1>(s, t);
+    out[0] = s[0] + t[0];
+  } else if constexpr (N <= 4) {
+    float a[2] = {v[0], v[1]}, b[2] = {v[2], v[N == 4 ? 3 : 1]};
+    permlane_swap_n32<2>(a, b);
+    float s[1] = {a[0] + b[0]}, t[1] = {a[1] + b[1]};
+    permlane_swap_n16<1>(s, t);
+    out[0] = s[0] + t[0];
+  } else {
+    float a[3] = {v[0], v[1], v[4]}, b[3] = {v[2], v[3], v[4]};
+    permlane_swap_n32<3>(a, b);
+    float s[2] = {a[0] + b[0], a[2] + b[2]};
+    float t[2] = {a[1] + b[1], s[1]};
+    permlane_swap_n16<2>(s, t);
+    out[0] = s[0] + t[0];
+    out[1] = s[1] + t[1];
+  }
+}
+
+// sum over the 16 lanes of a DPP row (fixed order; every lane gets the total)
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float x) {
+  return __builtin_bit_cast(
+      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float row_sum16(float v) {
+  v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += dpp_mov<0x141>(v);  // row_half_mirror
+  v += dpp_mov<0x140>(v);  // row_mirror
+  return v;
+}
+
+// the same row sums of NB different values (NB = 4, 8, 16) as a reduce-scatter:
+// at a level a lane keeps one value of a pair and adds its partner's copy of
+// it (the pair row_sum16 adds at that level, so the same bits), halving the
+// values in flight; once one value is left the remaining levels are
+// row_sum16's.  The partner of the two mirror levels differs in every lower
+// lane bit, so the kept half is chosen by c0 = b0 ^ b2, c1 = b1 ^ b2,
+// c2 = b2 ^ b3, b3 (b: bits of the lane's column), which a level's partner
+// shares below that level and flips at it.  The lane ends with the total of
+// v[row_scatter_own(col) % NB].
+struct RowSel {
+  bool c0, c1, c2, b3;
+};
+__device__ __forceinline__ RowSel row_scatter_sel(int col) {
+  return {((col ^ (col >> 2)) & 1) != 0, (((col >> 1) ^ (col >> 2)) & 1) != 0,
+          (((col >> 2) ^ (col >> 3)) & 1) != 0, (col & 8) != 0};
+}
+__device__ __forceinline__ int row_scatter_own(int col) {
+  return ((col ^ (col >> 2)) & 1) | ((((col >> 1) ^ (col >> 2)) & 1) << 1) |
+         ((((col >> 2) ^ (col >> 3)) & 1) << 2) | (col & 8);
+}
+template <int CTRL>
+__device__ __forceinline__ float row_scatter_step(bool sel, float a, float b) {
+  const float keep = sel ? b : a, send = sel ? a : b;
+  return keep + dpp_mov<CTRL>(send);
+}
+template <int NB>
+__device__ __forceinline__ float row_scatter16(const float* v, RowSel s) {
+  static_assert(NB == 4 || NB == 8 || NB == 16, "a power of two of values");
+  float w[NB / 2];
+#pragma unroll
+  for (int m = 0; m < NB / 2; ++m) w[m] = row_scatter_step<0xB1>(s.c0, v[2 * m], v[2 * m + 1]);
+#pragma unroll
+  for (int m = 0; m < NB / 4; ++m) w[m] = row_scatter_step<0x4E>(s.c1, w[2 * m], w[2 * m + 1]);
+  if constexpr (NB >= 8) {
+#pragma unroll
+    for (int m = 0; m < NB / 8; ++m) w[m] = row_scatter_step<0x141>(s.c2, w[2 * m], w[2 * m + 1]);
+  } else {
+    w[0] += dpp_mov<0x141>(w[0]);
+  }
+  if constexpr (NB == 16) {
+    w[0] = row_scatter_step<0x140>(s.b3, w[0], w[1]);
+  } else {
+    w[0] += dpp_mov<0x140>(w[0]);
+  }
+  return w[0];
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -687,6 +687,10 @@ __device__ __forceinline__ void load_tile_edges(const int* __restrict__ nbr,
 // 9.21 -> 9.01-9.11 ms for the three launches, same box (profiles/r06_s20_*);
 // in the last block's backward it measured neutral to slower and stays per
 // value
+// the forward's row sums are a reduce-scatter (sum_rows4_scatter): a path's D3
+// totals end up one per lane group, 3 swaps + 3 adds per four values instead of
+// 8 + 8 + 8 copies, and every group stores its own: middle forward 2.98 -> 2.83
+// ms per launch, first 1.04 -> 1.02, same bits (profiles/rowsum_*)
 // the middle and last blocks' two tiles go through the radial MLP together,
 // each W1 operand block loaded once for both (same products, same bits):
 // last-block forward 1.05-1.06 -> 1.00-1.01 ms, middle 9.13 -> 9.02 ms
@@ -802,14 +806,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd2Waves<L
               tp_acc4<p.l1, p.l2, p.l3>(x[0], lds[wid][0] + 4 * g * 9 + yoff(p.l2), 9, wv0, acc);
               if (two) tp_acc4<p.l1, p.l2, p.l3>(x[1], lds[wid][1] + 4 * g * 9 + yoff(p.l2), 9, wv1, acc);
               if constexpr (STAMPED) STAMP(3);   // tensor product
-              sum_rows4_n<D3>(acc);
-#pragma unroll
-              for (int k = 0; k < D3; ++k) {
-                const float v = acc[k] * rden;
-                if (g == 0) {
-                  float* a = acl + p.moff + (16 * j + col) * D3 + k;
-                  *a = first_tile ? v : *a + v;
-                }
+              // reduce-scatter over the lane groups: group g ends up with the
+              // total of component k = g and stores it, all groups at once.
+              // Groups left with a second copy of a total (D3 = 3: group 3
+              // holds component 1; D3 = 1 and component 4 of D3 = 5: every
+              // group) store it too -- the same bits to the same address --
+              // so no store needs a lane mask (masking the copies measured
+              // the same: 2.79 ms per middle launch either way)
+              float tot[(D3 + 3) / 4];
+              sum_rows4_scatter<D3>(acc, tot);
+              float* a0 = acl + p.moff + (16 * j + col) * D3;
+              {
+                const float v = tot[0] * rden;
+                float* a = a0 + (D3 == 1 ? 0 : D3 == 3 && g == 3 ? 1 : g);
+                *a = first_tile ? v : *a + v;
+              }
+              if constexpr (D3 == 5) {
+                const float v = tot[1] * rden;
+                a0[4] = first_tile ? v : a0[4] + v;
               }
               if constexpr (STAMPED) STAMP(5);   // row sums + LDS accumulation
             }
@@ -861,20 +875,6 @@ __device__ __forceinline__ float tp_bwd_xw(const float* x, const float* y, float
     dwv += x[i] * ui;
   });
   return dwv;
-}
-
-// sum over the 16 lanes of a DPP row (fixed order; every lane gets the total)
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float x) {
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row_sum16(float v) {
-  v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += dpp_mov<0x141>(v);  // row_half_mirror
-  v += dpp_mov<0x140>(v);  // row_mirror
-  return v;
 }
 
 // dE/dagg operands of path PN at channel block jj for the lane's edge (4 * D3
@@ -1057,6 +1057,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const __amdgpu_buffer_rsrc_t Rx = rsrc_bytes(h + (int64_t)jn * L::DX, L::DX * 4);
   const __amdgpu_buffer_rsrc_t Rg = rsrc_bytes(gagg, (int64_t)n_centers * L::DM * 4);
   for (int t = lane; t < L::DX; t += 64) dacc[t] = 0.f;
+  const RowSel rsel = row_scatter_sel(col);
+  const int own = row_scatter_own(col);
 
   for (int q0 = qb; q0 < qe; q0 += 32) {
     const bool two = q0 + 16 < qe;   // wave-uniform
@@ -1192,12 +1194,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
           });
           phase();
-          // both tiles' edges summed per lane already: one row sum over the 16
-          // edge lanes, lane c == 0 accumulates the node's row
-#pragma unroll
-          for (int i = 0; i < 4 * D1; ++i) {
-            const float v = row_sum16(dx[i]);
-            if (col == 0) dacc[XOFF + (16 * jj + 4 * g) * D1 + i] += v;
+          // both tiles' edges summed per lane already: the lane's 4 * D1
+          // values (4, 12 or 20) summed over the 16 edge lanes as a
+          // reduce-scatter in batches of 16 / 8 / 4 (row_sum16's pairs, the
+          // same bits), every lane accumulating the value it ends up owning
+          // (the lanes sharing a value of a short batch read, add and write
+          // the same bits); as all-reduces with lane c == 0 accumulating,
+          // this kernel ran 1.93 ms, so 1.80 (profiles/rowsum_kernel_stats_*)
+          {
+            constexpr int NV = 4 * D1;
+            static_assert(NV % 8 == 4, "batches of 16, 8, then 4");
+            float* da = dacc + XOFF + (16 * jj + 4 * g) * D1;
+            if constexpr (NV >= 16) da[own] += row_scatter16<16>(dx, rsel);
+            if constexpr (NV % 16 >= 8) da[NV / 16 * 16 + (own & 7)] += row_scatter16<8>(dx + NV / 16 * 16, rsel);
+            da[NV / 8 * 8 + (own & 3)] += row_scatter16<4>(dx + NV / 8 * 8, rsel);
           }
         }
       }
