@@ -39,6 +39,7 @@
 #include "neighbor.h"
 #include "tgemm.h"
 #include "tp.h"
+#include "w2_image.h"
 
 using namespace e3gnn;
 
@@ -186,8 +187,9 @@ struct e3gnn_model {
     DBuf w0, w1, w2, w0t, w1t, w2t;
     DBuf w1p, w2p, w2q, w2r;  // MFMA-operand orders of the fused kernels (fused.h)
     DBuf w2b;            // 3-way bf16 split of w2 in 16x16x32 operand order (fused.h)
-    DBuf w2d;            // the same for the fused backward's pairs (fused.h)
-    DBuf w2v;            // w2b's column blocks in visiting order (fused.h)
+    DBuf w2d;            // the same for the last block's backward pairs (fused.h)
+    DBuf w2v;            // w2b's column blocks in visiting order (last block; fused.h)
+    DBuf w2s;            // the lock-step backward's pair images (first / middle; w2_image.h)
     DBuf w1b, w1tb, w0tb;  // layer-1 / chain-backward operands, w2b order (fused.h)
   };
   std::vector<Mlp> mlp;
@@ -639,6 +641,7 @@ MlpW mlp_ptrs(const e3gnn_model* m, int t) {
               static_cast<const uint16_t*>(mm.w2b.p),
               static_cast<const uint16_t*>(mm.w2d.p),
               static_cast<const uint16_t*>(mm.w2v.p),
+              static_cast<const uint16_t*>(mm.w2s.p),
               static_cast<const uint16_t*>(mm.w1b.p),
               static_cast<const uint16_t*>(mm.w1tb.p),
               static_cast<const uint16_t*>(mm.w0tb.p)};
@@ -1061,31 +1064,44 @@ e3gnn_model* e3gnn_load(const char* weights_path, const char* manifest_path, int
         const std::vector<int> cols = bwd_w_block_cols(m->kcode(t));
         if ((int)cols.size() * 16 != W || cols.size() % 2)
           throw std::runtime_error("dE/dw block order does not cover the weights");
-        // w2d (MlpW::w2d): element t of lane (g, c) for hidden block bh is
-        // w2[16 bh + c][col], col = cols[2P] + 4g + t (t < 4) or cols[2P + 1] + 4g + t - 4
-        std::vector<float> d2((size_t)W * 64 * 3 / 2);
-        uint16_t* d2h = reinterpret_cast<uint16_t*>(d2.data());
-        for (size_t P = 0; P < cols.size() / 2; ++P)
-          for (int bh = 0; bh < 4; ++bh)
-            for (int g = 0; g < 4; ++g)
-              for (int c = 0; c < 16; ++c)
-                for (int t8 = 0; t8 < 8; ++t8) {
-                  const int col = t8 < 4 ? cols[2 * P] + 4 * g + t8 : cols[2 * P + 1] + 4 * g + t8 - 4;
-                  float v = a2[(size_t)(16 * bh + c) * W + col];
-                  for (int pc = 0; pc < 3; ++pc) {
-                    const uint16_t hb = bf16_rne(v);
-                    d2h[(((P * 3 + pc) * 4 + bh) * 64 + g * 16 + c) * 8 + t8] = hb;
-                    v -= bf16_to_f32(hb);
+        // the last block's backward (k_conv_bwd_nbr) reads its operands from
+        // L2 in the lane orders w2d and w2v; the first and middle blocks'
+        // (k_conv_bwd_ls) stage one image per pair that serves both (w2s)
+        if (m->kcode(t) % 3 == 2) {
+          // w2d (MlpW::w2d): element t of lane (g, c) for hidden block bh is
+          // w2[16 bh + c][col], col = cols[2P] + 4g + t (t < 4) or cols[2P + 1] + 4g + t - 4
+          std::vector<float> d2((size_t)W * 64 * 3 / 2);
+          uint16_t* d2h = reinterpret_cast<uint16_t*>(d2.data());
+          for (size_t P = 0; P < cols.size() / 2; ++P)
+            for (int bh = 0; bh < 4; ++bh)
+              for (int g = 0; g < 4; ++g)
+                for (int c = 0; c < 16; ++c)
+                  for (int t8 = 0; t8 < 8; ++t8) {
+                    const int col = t8 < 4 ? cols[2 * P] + 4 * g + t8 : cols[2 * P + 1] + 4 * g + t8 - 4;
+                    float v = a2[(size_t)(16 * bh + c) * W + col];
+                    for (int pc = 0; pc < 3; ++pc) {
+                      const uint16_t hb = bf16_rne(v);
+                      d2h[(((P * 3 + pc) * 4 + bh) * 64 + g * 16 + c) * 8 + t8] = hb;
+                      v -= bf16_to_f32(hb);
+                    }
                   }
-                }
-        if (upload(mm.w2d, d2) != hipSuccess) throw std::runtime_error("upload mlp (w2d)");
-        // w2v (MlpW::w2v): w2b's blocks in the visiting order of the kernels
-        {
+          if (upload(mm.w2d, d2) != hipSuccess) throw std::runtime_error("upload mlp (w2d)");
+          // w2v (MlpW::w2v): w2b's blocks in the visiting order of the kernels
           std::vector<float> v2(b2.size());
           const size_t blk = (size_t)64 * 16 * 3 / 2;   // floats per column block
           for (size_t k = 0; k < cols.size(); ++k)
             std::memcpy(v2.data() + k * blk, b2.data() + (size_t)(cols[k] / 16) * blk, blk * 4);
           if (upload(mm.w2v, v2) != hipSuccess) throw std::runtime_error("upload mlp (w2v)");
+        } else {
+          // w2s (MlpW::w2s): per pair P and piece, the [hidden unit][channel]
+          // matrix of the pair's 2 x 16 columns cols[2P], cols[2P + 1] in the
+          // swizzled order of w2_image.h, the same residual chain of bf16
+          // pieces: read by rows it gives w2d's lane registers, read
+          // transposed (ds_read_b64_tr_b16) w2v's
+          const size_t npairs = cols.size() / 2;
+          std::vector<float> s2(npairs * w2img::PAIR_BYTES / 4);
+          w2img::pack(a2.data(), W, cols.data(), (int)npairs, reinterpret_cast<uint16_t*>(s2.data()));
+          if (upload(mm.w2s, s2) != hipSuccess) throw std::runtime_error("upload mlp (w2s)");
         }
         if (W % 16 || upload(mm.w1p, kperm(a1, 64)) != hipSuccess ||
             upload(mm.w2p, kperm(a2, W)) != hipSuccess || upload(mm.w2q, q2) != hipSuccess ||

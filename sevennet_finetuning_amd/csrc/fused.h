@@ -18,14 +18,20 @@ struct MlpW {
   // w2 as three bf16 pieces (w2 = p0 + p1 + p2, exact) in v_mfma_f32_16x16x32_bf16
   // operand order: [n/16][piece][m][g][c][t] = piece of w2[16(2m + t/4) + 4g + t%4][n]
   const uint16_t* w2b;
-  // the lock-step backward's dH2 operand over PAIRS of consecutive visited
-  // 16-column blocks (api.cpp bwd_w_block_cols): [pair][piece][bh][g][c][t] = piece of
+  // the last block's dH2 operand over PAIRS of consecutive visited 16-column
+  // blocks (api.cpp bwd_w_block_cols): [pair][piece][bh][g][c][t] = piece of
   // w2[16 bh + c][col], col = channel 4g + t of the pair's first block (t < 4)
-  // or 4g + t - 4 of its second
+  // or 4g + t - 4 of its second (last block only; null elsewhere)
   const uint16_t* w2d;
   // w2b's column blocks in the kernels' visiting order (block k at column 16 k):
   // the software-pipelined loops fetch the operand of the block after next
+  // (last block only; null elsewhere)
   const uint16_t* w2v;
+  // the lock-step backward's one image per PAIR (w2_image.h): [pair][piece]
+  // [hidden unit][swizzled 8-byte unit of 4 channels of one of the pair's two
+  // blocks], staged in LDS by a straight copy; its row reads are w2d's lane
+  // registers, its transposed reads w2v's (first / middle blocks only)
+  const uint16_t* w2s;
   // the radial MLP's other bf16x6 products, in w2b's operand order: W1 (layer
   // 1 forward, 64 columns), W1^T (dH1 = dA2 W1^T) and W0^T padded to 16 columns
   // (demb = dA1 W0^T)

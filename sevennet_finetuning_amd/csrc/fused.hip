@@ -30,6 +30,7 @@
 #include "common.h"
 #include "fused.h"
 #include "tp.h"
+#include "w2_image.h"
 
 #include <type_traits>
 
@@ -994,9 +995,7 @@ __device__ __forceinline__ void mlp_bwd_chain(const WRes& R, const float* __rest
 // keeping layer 0's as well measured slower)
 // the same old-value reads for the last block's per-pass dE/du and dE/demb
 // (2.13 -> 2.09-2.12 ms, same box; profiles/r06_s12_*)
-constexpr int LS_BLK = 6144;            // bytes of one w2v column block (3 pieces x 2 halves x 1 KB)
-constexpr int LS_PAIR_W = 2 * LS_BLK;   // the pair's two w-recompute operand blocks
-constexpr int LS_PAIR_D = 12288;        // the pair's dH2 operand (w2d: 3 pieces x 4 bh x 1 KB)
+constexpr int LS_PAIR_D = 12288;       // the pair's dH2 operand (w2d: 3 pieces x 4 bh x 1 KB)
 
 // dH2^T += W2[:, pair] dw^T on three bf16 products with the pair's W2 pieces
 // read from global memory (L2: every wave of the launch reads the same
@@ -1256,28 +1255,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // 2 x 16 x 32 on f32 MFMA.  Middle blocks: two workgroups per CU (LDS), 2 waves
 // per SIMD; the first block: 3 waves per SIMD.
 
-// The staged image holds only the pieces the backward's products read: with
-// the three-product forms (E3GNN_BWD_W_X3, E3GNN_DH2_X3) pieces 0 and 1 of
-// each operand, 16 KB per pair instead of 24
-constexpr int LS_WPC = E3GNN_BWD_W_X3 ? 2 : 3;   // staged pieces of a w-recompute block
-constexpr int LS_DPC = E3GNN_DH2_X3 ? 2 : 3;     // of the pair's dH2 operand
-constexpr int LS_IBLK = LS_WPC * 2048;   // image bytes of one w-recompute block (pieces x 2 halves x 1 KB)
-constexpr int LS_IW = 2 * LS_IBLK;       // the pair's w-recompute part
-constexpr int LS_IMG = LS_IW + LS_DPC * 4096;   // + the dH2 part (pieces x 4 bh x 1 KB)
+// The pair's W2 pieces are staged ONCE, as the [hidden][channel] image of
+// w2_image.h (MlpW::w2s): dH2 reads it by rows, the w recompute transposed
+// (ds_read_b64_tr_b16), each getting the operand registers of the w2d / w2v
+// orders.  The image holds only the pieces the backward's products read: with
+// the three-product forms (E3GNN_BWD_W_X3, E3GNN_DH2_X3) pieces 0 and 1, 8 KB
+// per pair (12 KB when either product runs on six)
+constexpr int LS_WPC = E3GNN_BWD_W_X3 ? 2 : 3;   // pieces the w recompute reads
+constexpr int LS_DPC = E3GNN_DH2_X3 ? 2 : 3;     // pieces dH2 reads
+constexpr int LS_IMG = (LS_WPC > LS_DPC ? LS_WPC : LS_DPC) * w2img::PIECE_BYTES;
 
+// the w-recompute operand of the pair's block b (transposed reads: every lane
+// of the wave active)
 template <int NPC = 3>
-__device__ __forceinline__ void lds_op3(Op3& o, const char* blk, int lane) {
+__device__ __forceinline__ void lds_op3(Op3& o, const char* pimg, int b, int lane) {
 #pragma unroll
   for (int pc = 0; pc < NPC; ++pc)
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
-      o.v[pc][m] = *reinterpret_cast<const bf16x8*>(blk + ((pc * 2 + m) * 64 + lane) * 16);
+    for (int m = 0; m < 2; ++m) o.v[pc][m] = w2img::tr_read(pimg, lane, b, pc, m);
 }
 
 // dH2^T += W2[:, pair] dw^T on bf16 MFMA (K = 32: element t of lane (g, c) is
 // channel 4g + t of the pair's first block (t < 4) or 4g + t - 4 of its second,
-// the w2d order); A = the W2 pieces (LDS), B = dw split in pieces (three
-// products by default, six with E3GNN_DH2_X3=0)
+// the w2d order); A = the W2 pieces (row reads of the LDS image), B = dw split
+// in pieces (three products by default, six with E3GNN_DH2_X3=0)
 __device__ __forceinline__ void dh2_pair(f32x4 (&dh2)[4], const float (&da)[4], const float (&db)[4],
                                          const char* pimg, int lane) {
   if constexpr (E3GNN_DH2_X3) {
@@ -1295,7 +1296,7 @@ __device__ __forceinline__ void dh2_pair(f32x4 (&dh2)[4], const float (&da)[4], 
     for (int bh = 0; bh < 4; ++bh)
 #pragma unroll
       for (int pc = 0; pc < 2; ++pc)
-        a[bh][pc] = *reinterpret_cast<const bf16x8*>(pimg + ((pc * 4 + bh) * 64 + lane) * 16);
+        a[bh][pc] = w2img::row_read(pimg, lane, pc, bh);
     phase();
 #pragma unroll
     for (int bh = 0; bh < 4; ++bh) {
@@ -1318,7 +1319,7 @@ __device__ __forceinline__ void dh2_pair(f32x4 (&dh2)[4], const float (&da)[4], 
     bf16x8 a[3];
 #pragma unroll
     for (int pc = 0; pc < 3; ++pc)
-      a[pc] = *reinterpret_cast<const bf16x8*>(pimg + ((pc * 4 + bh) * 64 + lane) * 16);
+      a[pc] = w2img::row_read(pimg, lane, pc, bh);
 #pragma unroll
     for (int q = 0; q < 6; ++q) dh2[bh] = mfma16(a[I[q]], d[J[q]], dh2[bh]);
   }
@@ -1342,9 +1343,9 @@ __device__ __forceinline__ int ls_tiles(const int* __restrict__ row_ptr, int cb,
 // structure as the forward (both blocks' w formed at the pair start, next
 // group's neighbour rows prefetched); dH2 of the pair on bf16x6 at its end.
 // waves per SIMD: the first block (128 input channels, 1,152 message channels:
-// 42 KB of LDS per workgroup) runs three (168 VGPRs with a few spills
-// measured 2.57 -> 2.27 ms against two), the middle blocks two (225 VGPRs;
-// their 80.9 KB of LDS allows no more)
+// 34.8 KB of LDS per workgroup, two images) runs three (168 VGPRs with a few
+// spills measured 2.57 -> 2.27 ms against two), the middle blocks two (their
+// 230 VGPRs allow no more; 64.5 KB of LDS per workgroup)
 template <class L>
 struct BwdLsWaves {
   static constexpr int v = L::KIND == 0 ? 3 : 2;
@@ -1358,21 +1359,22 @@ constexpr int LS_WPG = 4;
 // waits leave the neighbour-row prefetch and the dE/dx stores in flight) and
 // written into one of TWO images before the pair's ONE barrier -- the other
 // image is the one the previous pair read, retired by the previous pair's
-// barrier.  The two images need 16 KB more LDS; in the middle blocks the
-// 0e x 0e -> 0e path's dE/dagg (C0 floats, moff 0) is then read from L2 with
-// the neighbour-row prefetch instead of staged, so two workgroups still fit a
-// CU (2 x 80.9 KB of 160 KB).  Elsewhere (and with the three-piece images of
-// the six-product build, which never fit twice): one image, written between
-// two barriers per pair.  Writing the images by LDS-DMA straight from L2 was
+// barrier.  The two images are 2 x 8 KB (2 x 12 KB in the six-product
+// builds); in the middle blocks the 0e x 0e -> 0e path's dE/dagg (C0 floats,
+// moff 0) is read from L2 with the neighbour-row prefetch instead of staged (a
+// choice made when the pair was staged as two 16 KB images and two workgroups
+// would not otherwise fit a CU; SevenNet-0's middle block is now 2 x 64.5 KB
+// of 160 KB, and staging the slice again measured no gain: DESIGN.md 8 item
+// 1).  Where two images do not fit: one image, written between two
+// barriers per pair.  Writing the images by LDS-DMA straight from L2 was
 // measured and rejected (5.68 -> 5.77 ms: its explicit wait before the barrier
 // drains every load and store in flight).
 template <class L>
 struct LsTwoImages {
-  static constexpr bool lean = LS_WPC == 2 && LS_DPC == 2;   // two-piece images
   static constexpr int OFF0 = L::KIND == 1 ? L::P[0].mul : 0;   // path 0 (l 0 0 0, moff 0): C0 floats
   static constexpr int DMS = L::DM - OFF0;                       // staged dE/dagg floats per centre
   static constexpr int bytes = LS_WPG * DMS * 4 + 2 * LS_IMG;
-  static constexpr bool v = lean && BwdLsWaves<L>::v * bytes <= 163840;
+  static constexpr bool v = BwdLsWaves<L>::v * bytes <= 163840;
 };
 // wave priority, raised around the lock-step backward's MFMA bursts
 template <int P>
@@ -1386,10 +1388,10 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
   constexpr int NBLK = L::W / 16, NPAIR = NBLK / 2;
   static_assert(NBLK % 2 == 0, "weight blocks come in pairs");
   constexpr int WPG = LS_WPG, NT = 64 * WPG;
-  // staging pieces (b128) of a pair: the w-recompute operands (NW per thread),
-  // then the dH2 ones (NST per thread in all)
-  constexpr int NWP = LS_IW / 16, NW = NWP / NT, NST = LS_IMG / 16 / NT, PB = LS_IBLK / 16;
-  static_assert(LS_IMG / 16 % NT == 0 && NWP % NT == 0 && PB % 64 == 0, "staging pieces per thread");
+  // staging pieces (b128) of a pair's image per thread: a straight copy of
+  // the first LS_IMG bytes of the pair in MlpW::w2s
+  constexpr int NST = LS_IMG / 16 / NT;
+  static_assert(LS_IMG / 16 % NT == 0, "staging pieces per thread");
   constexpr bool TWO = LsTwoImages<L>::v;   // two images, one barrier per pair
   // tile-start values kept in registers to the tile end (the first block at
   // three waves per SIMD: no VGPRs to spare)
@@ -1417,17 +1419,12 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
   const __amdgpu_buffer_rsrc_t Rg0 =
       rsrc_bytes(gagg + (valid ? (int64_t)c * L::DM : 0), valid ? (int64_t)OFF0 * 4 : 0);
   const WRes R = make_wres(W, L::W);
+  const __amdgpu_buffer_rsrc_t Rs = rsrc_bytes(W.w2s, NPAIR * w2img::PAIR_BYTES);   // the pair images
   const __amdgpu_buffer_rsrc_t Rx = rsrc_bytes(h, (int64_t)n_nodes * L::DX * 4);
   f32x4 st[NST];
   auto issue = [&](int P) {
-    // image piece idx: w-recompute block idx / PB (its first LS_WPC pieces
-    // in the w2v order), then the dH2 operand's first LS_DPC pieces (w2d);
-    // each thread's pieces are all W, then all D
-    auto wsrc = [&](int idx) { return (idx / PB) * LS_BLK + (idx % PB) * 16; };
 #pragma unroll
-    for (int i = 0; i < NW; ++i) st[i] = ldw4(R.w2v, wsrc(tid + NT * i), P * LS_PAIR_W);
-#pragma unroll
-    for (int i = NW; i < NST; ++i) st[i] = ldw4(R.w2d, (tid + NT * i - NWP) * 16, P * LS_PAIR_D);
+    for (int i = 0; i < NST; ++i) st[i] = ldw4(Rs, (tid + NT * i) * 16, P * w2img::PAIR_BYTES);
   };
   // the single image: the previous pair's reads retired, the pair written, published
   auto commit = [&]() {
@@ -1566,8 +1563,8 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
                   if (act) {
                     ls_prio<1>();   // MFMA bursts first
                     Op3 wq, wq1;   // both blocks' pieces read first
-                    lds_op3<LS_WPC>(wq, pimg, lane);
-                    lds_op3<LS_WPC>(wq1, pimg + LS_IBLK, lane);
+                    lds_op3<LS_WPC>(wq, pimg, 0, lane);
+                    lds_op3<LS_WPC>(wq1, pimg, 1, lane);
                     phase();
                     wv0 = w2_block_bwd<false>(hq, wq);
                     wv1 = w2_block_bwd<false>(hq, wq1);
@@ -1594,7 +1591,7 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
                   if constexpr (ODD) {
                     if constexpr (STAMPED) STAMP(5);   // tensor product (+ stores)
                     ls_prio<1>();   // MFMA bursts first
-                    dh2_pair(dh2, dwp, dwr, pimg + LS_IW, lane);
+                    dh2_pair(dh2, dwp, dwr, pimg, lane);
                     ls_prio<0>();
                     if constexpr (STAMPED) STAMP(4);   // dH2 (split + MFMA)
                   } else {
