@@ -29,6 +29,8 @@
  *   e3nn normalize2mom(silu) and its derivatives (training)          e3gnn_act
  *   EquivariantGate / e3nn Gate and its derivatives (training)       e3gnn_gate
  *   second-order fine-tune derivatives, hand-scheduled (training)   e3gnn_act_dual, e3gnn_gate_dual
+ *   FCN_e3nn readout and Linear biases in those derivatives         e3gnn_fcn_train_*,
+ *     (nn/linear.py:94-129, model_build.py:194-240)                  e3gnn_colsum_grouped
  *   LAMMPS pair_style d3 settings/coeff, compute/update             e3gnn_d3_create /
  *     (pair_d3.cu:265-767, :2003-2056)                               e3gnn_d3_compute
  *   error->all(FLERR, msg)                                           return code +
@@ -442,6 +444,45 @@ int e3gnn_act_dual(int64_t n, const float* x, const float* xd, const float* g, c
 int e3gnn_gate_dual(int op, int64_t n, const int32_t* dims, const float* y, const float* yd,
                     const float* xb, const float* xdb, float* out0, float* out1, float scale,
                     void* stream);
+
+/* Column sums of up to 16 row-major blocks in one launch, dst[c] += sum_r
+ * src[r ld + c] for c < cols: the linear biases' gradients of the fine-tune
+ * step (fixed-order sums, no atomics; the dst ranges must not overlap). */
+typedef struct e3gnn_colsum_desc {
+  const float* src;
+  float* dst;
+  int64_t ld;
+  int32_t rows, cols;
+} e3gnn_colsum_desc;
+int e3gnn_colsum_grouped(int n, const e3gnn_colsum_desc* blocks, void* stream);
+
+/* The FCN readout (readout_as_fcn; e3nn FullyConnectedNet without biases) in
+ * the fine-tune step.  widths[0 .. n_hidden] = the input row D and the hidden
+ * widths (1 .. 128 each, n_hidden 1 .. 4), act = 0 relu, 1 silu, 2 tanh,
+ * 3 sigmoid, 4 abs, 5 elu, act_norm its normalize2mom constant c:
+ *   z_k = a_{k-1} M_{k-1}, a_k = c f(z_k) (a_0 = x), s = a_nh . v.
+ * weights: e3gnn_fcn_packed_floats() floats -- M_k [widths[k]][widths[k+1] | 1]
+ * row-major (padding zero) for k < n_hidden, then v; every matrix already
+ * scaled by 1 / sqrt(fan_in).  With pre_k = widths[1] + .. + widths[k-1]:
+ *   z, zd  layer k at n pre_k,  [n, widths[k]]: z_k and its tangent z'_k
+ *   a, zb  layer k at 2n pre_k, [2n, widths[k]]: rows [0, n) a_k / z-bar_k,
+ *          rows [n, 2n) a'_k / z'-bar_k
+ * _forward: x [n, D] -> z, a (primal rows), s [n], and dx [n, D] = seed[i]
+ *   ds/dx (dx null: skipped; seed null: 1).
+ * _tangent: xd [n, D] -> zd, a (tangent rows), sd [n] (a'_k = c f'(z_k) z'_k).
+ * _dual: the reverse of (s, s') seeded with (sb, sbd) [n]: zb, and xb [2n, D]
+ *   (z'-bar_k = c f' a'-bar_k, z-bar_k = c f' a-bar_k + c f'' z'_k a'-bar_k).
+ * One launch each, fixed-order sums, no allocation or synchronisation. */
+int64_t e3gnn_fcn_packed_floats(int n_hidden, const int32_t* widths);
+int e3gnn_fcn_train_forward(int64_t n, int n_hidden, const int32_t* widths, int act, float act_norm,
+                            const float* weights, const float* x, const float* seed, float* z, float* a,
+                            float* s, float* dx, void* stream);
+int e3gnn_fcn_train_tangent(int64_t n, int n_hidden, const int32_t* widths, int act, float act_norm,
+                            const float* weights, const float* xd, const float* z, float* zd, float* a,
+                            float* sd, void* stream);
+int e3gnn_fcn_train_dual(int64_t n, int n_hidden, const int32_t* widths, int act, float act_norm,
+                         const float* weights, const float* sb, const float* sbd, const float* z,
+                         const float* zd, float* zb, float* xb, void* stream);
 
 /* ---- device neighbour list (the graph build in front of the hot path) ----
  * Replaces ASE primitive_neighbor_list('ijDS', pbc, cell, pos, cutoff,

@@ -86,6 +86,11 @@ SIGNATURES = {
     'e3gnn_gate': (_c_int, [_c_int, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_f, _vp]),
     'e3gnn_act_dual': (_c_int, [_c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_f, _vp]),
     'e3gnn_gate_dual': (_c_int, [_c_int, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_f, _vp]),
+    'e3gnn_colsum_grouped': (_c_int, [_c_int, _vp, _vp]),
+    'e3gnn_fcn_packed_floats': (_c_i64, [_c_int, _vp]),
+    'e3gnn_fcn_train_forward': (_c_int, [_c_i64, _c_int, _vp, _c_int, _c_f] + [_vp] * 8),
+    'e3gnn_fcn_train_tangent': (_c_int, [_c_i64, _c_int, _vp, _c_int, _c_f] + [_vp] * 7),
+    'e3gnn_fcn_train_dual': (_c_int, [_c_i64, _c_int, _vp, _c_int, _c_f] + [_vp] * 8),
     'e3gnn_d3_create': (_vp, [_c_int, _c_int, _vp, _c_f, _c_f, _c_int, _vp, _vp, _vp, _vp, _vp]),
     'e3gnn_d3_free': (None, [_vp]),
     'e3gnn_d3_compute': (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -132,6 +137,12 @@ class GemmDesc(ctypes.Structure):
                 ('trans_b', ctypes.c_int32), ('trans_a2', ctypes.c_int32),
                 ('trans_b2', ctypes.c_int32), ('alpha', ctypes.c_float), ('beta', ctypes.c_int32),
                 ('krange', _vp), ('krange_stride_m', ctypes.c_int32), ('layout', _vp)]
+
+
+class ColsumDesc(ctypes.Structure):
+    """e3gnn_colsum_desc (include/e3gnn.h)"""
+    _fields_ = [('src', _vp), ('dst', _vp), ('ld', _c_i64), ('rows', ctypes.c_int32),
+                ('cols', ctypes.c_int32)]
 
 
 class E3GNNError(RuntimeError):

@@ -29,6 +29,7 @@
 #include "d3.h"
 #include "dbuf.h"
 #include "fcn_act.h"
+#include "fcn_train.h"
 #include "generic.h"
 #include "train_ops.h"
 #include "common.h"
@@ -2454,6 +2455,78 @@ int e3gnn_gate_dual(int op, int64_t n, const int32_t* dims, const float* y, cons
   if (n > 0 && (!y || !yd || !out0 || (op == 1 && (!xb || !xdb || !out1))))
     return fail(E3GNN_ERR_ARG, "null gate operand");
   HIPCHK(launch_gate_dual(op, n, dims, y, yd, xb, xdb, out0, out1, scale, (hipStream_t)stream));
+  return E3GNN_OK;
+}
+
+int e3gnn_colsum_grouped(int n, const e3gnn_colsum_desc* blocks, void* stream) {
+  if (n < 0 || n > COLSUM_MAX || (n > 0 && !blocks))
+    return fail(E3GNN_ERR_ARG, "e3gnn_colsum_grouped: 0.." + std::to_string(COLSUM_MAX) + " blocks");
+  ColsumBatch b{};
+  for (int i = 0; i < n; ++i) {
+    const e3gnn_colsum_desc& d = blocks[i];
+    if (d.rows < 0 || d.cols < 0 || d.ld < d.cols || (d.rows > 0 && d.cols > 0 && (!d.src || !d.dst)))
+      return fail(E3GNN_ERR_ARG, "e3gnn_colsum_grouped: block " + std::to_string(i));
+    b.p[i] = ColsumProb{d.src, d.dst, d.ld, d.rows, d.cols};
+  }
+  b.n = n;
+  HIPCHK(launch_colsum(b, (hipStream_t)stream));
+  return E3GNN_OK;
+}
+
+// the FCN readout of the fine-tune step (fcn_train.hip): the inference
+// kernel's limits (node.h FcnDims)
+static int fcn_train_dims(int64_t n, int nh, const int32_t* widths, int act, float act_norm, FcnDims& d) {
+  if (n < 0 || n > 0x7fffffff) return fail(E3GNN_ERR_ARG, "fcn_train: bad row count");
+  if (nh < 1 || nh > FCN_MAX_HIDDEN || !widths)
+    return fail(E3GNN_ERR_ARG, "fcn_train: 1.." + std::to_string(FCN_MAX_HIDDEN) + " hidden layers");
+  if (act < 0 || act >= FCN_ACT_KINDS) return fail(E3GNN_ERR_ARG, "fcn_train: unknown activation");
+  d = FcnDims{};
+  d.nh = nh;
+  for (int k = 0; k <= nh; ++k) {
+    if (widths[k] < 1 || widths[k] > FCN_MAX_WIDTH)
+      return fail(E3GNN_ERR_ARG, "fcn_train: widths of 1.." + std::to_string(FCN_MAX_WIDTH));
+    d.w[k] = widths[k];
+  }
+  d.kind = act;
+  d.c = act_norm;
+  return E3GNN_OK;
+}
+
+int64_t e3gnn_fcn_packed_floats(int n_hidden, const int32_t* widths) {
+  FcnDims d;
+  if (fcn_train_dims(0, n_hidden, widths, 0, 1.f, d)) return -1;
+  return d.padded_floats();
+}
+
+int e3gnn_fcn_train_forward(int64_t n, int n_hidden, const int32_t* widths, int act, float act_norm,
+                            const float* weights, const float* x, const float* seed, float* z, float* a,
+                            float* s, float* dx, void* stream) {
+  FcnDims d;
+  if (int rc = fcn_train_dims(n, n_hidden, widths, act, act_norm, d)) return rc;
+  if (n > 0 && (!weights || !x || !z || !a || !s)) return fail(E3GNN_ERR_ARG, "fcn_train_forward: null operand");
+  HIPCHK(launch_fcn_train_fwd((int)n, d, weights, x, seed, z, a, s, dx, (hipStream_t)stream));
+  return E3GNN_OK;
+}
+
+int e3gnn_fcn_train_tangent(int64_t n, int n_hidden, const int32_t* widths, int act, float act_norm,
+                            const float* weights, const float* xd, const float* z, float* zd, float* a,
+                            float* sd, void* stream) {
+  FcnDims d;
+  if (int rc = fcn_train_dims(n, n_hidden, widths, act, act_norm, d)) return rc;
+  if (n > 0 && (!weights || !xd || !z || !zd || !a || !sd))
+    return fail(E3GNN_ERR_ARG, "fcn_train_tangent: null operand");
+  HIPCHK(launch_fcn_train_tangent((int)n, d, weights, xd, z, zd, a, sd, (hipStream_t)stream));
+  return E3GNN_OK;
+}
+
+int e3gnn_fcn_train_dual(int64_t n, int n_hidden, const int32_t* widths, int act, float act_norm,
+                         const float* weights, const float* sb, const float* sbd, const float* z,
+                         const float* zd, float* zb, float* xb, void* stream) {
+  FcnDims d;
+  if (int rc = fcn_train_dims(n, n_hidden, widths, act, act_norm, d)) return rc;
+  if (n > 0 && (!weights || !sb || !sbd || !z || !zd || !zb || !xb))
+    return fail(E3GNN_ERR_ARG, "fcn_train_dual: null operand");
+  HIPCHK(launch_fcn_train_dual((int)n, d, weights, sb, sbd, z, zd, zb, xb, (hipStream_t)stream));
   return E3GNN_OK;
 }
 

@@ -41,4 +41,25 @@ __device__ __forceinline__ void fcn_act(int kind, float z, float& f, float& df) 
   }
 }
 
+// f''(z), for the fine-tune step's dual reverse of the readout (fcn_train.hip)
+__device__ __forceinline__ float fcn_act2(int kind, float z) {
+  switch (kind) {
+    case 0: return 0.f;
+    case 1: {
+      const float sg = 1.f / (1.f + __expf(-z));
+      return sg * (1.f - sg) * (2.f + z * (1.f - 2.f * sg));
+    }
+    case 2: {
+      const float t = tanhf(z);
+      return -2.f * t * (1.f - t * t);
+    }
+    case 3: {
+      const float sg = 1.f / (1.f + __expf(-z));
+      return sg * (1.f - sg) * (1.f - 2.f * sg);
+    }
+    case 4: return 0.f;
+    default: return z > 0.f ? 0.f : __expf(z);
+  }
+}
+
 }  // namespace e3gnn

@@ -49,4 +49,18 @@ struct LossArgs {
 hipError_t launch_loss_efs(const LossArgs& a, hipStream_t s);
 hipError_t launch_ewc_flat(int64_t n, const float* th, const float* f, const float* o, const float* ft,
                            float lam, float* grad, float* part, hipStream_t s);
+// dst[c] += sum_r src[r ld + c] (c < cols) for every block of the batch: one
+// launch, fixed-order sums (the linear biases' gradients of the explicit step)
+constexpr int COLSUM_MAX = 16;
+struct ColsumProb {
+  const float* src;
+  float* dst;
+  int64_t ld;
+  int rows, cols;
+};
+struct ColsumBatch {
+  ColsumProb p[COLSUM_MAX];
+  int n;
+};
+hipError_t launch_colsum(const ColsumBatch& b, hipStream_t s);
 }  // namespace e3gnn

@@ -53,6 +53,31 @@ __global__ void k_act_dual(int64_t n, const float* __restrict__ x, const float* 
   ogd[i] = gd[i] * d1;
 }
 
+// Column sums of up to COLSUM_MAX row-major blocks in one launch (the linear
+// biases' gradients: dst[c] += sum_r src[r ld + c]).  A workgroup owns 64
+// columns of one block: thread (q, c) sums the rows q, q + 16, ... in ascending
+// order (the fine-tune batch's 432 rows: 27 dependent adds per thread) and the
+// sixteen partial sums are added in the order q = 0 .. 15 -- fixed order, no
+// atomics; every dst column has exactly one writer.
+constexpr int COLSUM_LANES = 16;
+__global__ __launch_bounds__(64 * COLSUM_LANES) void k_colsum(ColsumBatch b) {
+  __shared__ float part[COLSUM_LANES][64];
+  const ColsumProb p = b.p[blockIdx.y];
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
+  if (blockIdx.x * 64 >= p.cols) return;   // (the whole workgroup)
+  float s = 0.f;
+  if (c < p.cols)
+    for (int r = q; r < p.rows; r += COLSUM_LANES) s += p.src[(int64_t)r * p.ld + c];
+  part[q][threadIdx.x & 63] = s;
+  __syncthreads();
+  if (q == 0 && c < p.cols) {
+    float t = part[0][c & 63];
+#pragma unroll
+    for (int i = 1; i < COLSUM_LANES; ++i) t += part[i][c & 63];
+    p.dst[c] += t;
+  }
+}
+
 }  // namespace
 
 hipError_t launch_act_dual(int64_t n, const float* x, const float* xd, const float* g,
@@ -72,6 +97,14 @@ hipError_t launch_act(int op, int64_t n, const float* x, const float* g, const f
     case 1: hipLaunchKernelGGL(k_act_bwd, grid, block, 0, s, n, x, g, out0, c); break;
     default: hipLaunchKernelGGL(k_act_bwd2, grid, block, 0, s, n, x, g, gg, out0, out1, c); break;
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_colsum(const ColsumBatch& b, hipStream_t s) {
+  int cols = 0;
+  for (int i = 0; i < b.n; ++i) cols = b.p[i].cols > cols ? b.p[i].cols : cols;
+  if (b.n <= 0 || cols <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_colsum, dim3((cols + 63) / 64, b.n), dim3(64 * COLSUM_LANES), 0, s, b);
   return hipGetLastError();
 }
 

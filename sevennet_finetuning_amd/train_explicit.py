@@ -32,7 +32,11 @@ the tests compare this module in float64 with autograd of the trainable
 model).
 
 Scope: SevenNet-0's architecture (nn.sevennet0_kinds, linear
-self-connection, XPLOR cutoff, normalised or raw SH, silu gates); other
+self-connection, XPLOR cutoff, normalised or raw SH, silu gates), with or
+without linear biases (``use_bias_in_linear``: a row-broadcast add on the
+primal rows, its gradient a column sum of the primal cotangent) and with the
+linear or the FCN readout (``readout_as_fcn`` within the readout kernel's
+limits, 1-4 hidden layers of 1-128 units: _Fcn, csrc/fcn_train.hip); other
 members of the family keep the autograd path.
 """
 import ctypes
@@ -59,9 +63,11 @@ def supported(model):
         return False
     if model.sc_type != 'linear' or model.cut.get('name', 'XPLOR') != 'XPLOR':
         return False
-    # linear biases / the FCN readout: the autograd path (their derivatives
-    # are not in the hand-scheduled sweep)
-    if getattr(model, 'use_bias', False) or model.readout_cfg.get('type', 'linear') != 'linear':
+    # linear biases on leading 0e columns; the FCN readout within the limits
+    # of its kernels (csrc/fcn_train.hip, as the inference kernel's)
+    if _bias_map(model) is None:
+        return False
+    if model.readout_cfg.get('type', 'linear') != 'linear' and _fcn_spec(model) is None:
         return False
     if model.lmax_edge != 2 or model.filter_parity != 1:
         return False
@@ -70,6 +76,229 @@ def supported(model):
         if not natural or gate_p != 1 or any(t[2] != 1 for t in scal) or len(gated) > 2:
             return False
     return True
+
+
+def _zero_e_prefix(irreps):
+    """the number of (l, p) = (0, +1) columns of a row of these irreps when
+    they lead it (the natural layouts), else None"""
+    k, other = 0, False
+    for mul, l, p in irreps:
+        if (l, p) == (0, 1):
+            if other:
+                return None
+            k += mul
+        else:
+            other = True
+    return k
+
+
+def _bias_map(model):
+    """key -> (parameter name, biased leading columns) of every linear of the
+    model that has a bias ({} without use_bias_in_linear); None when a bias
+    meets columns that do not lead its row"""
+    if not getattr(model, 'use_bias', False):
+        return {}
+    hid = [(model.readout_hidden, 0, 1)]
+    lins = [('emb', 'onehot_to_feature_x', model.irreps[0]),
+            ('r1', 'reduce_input_to_hidden', hid), ('r2', 'reduce_hidden_to_energy', [(1, 0, 1)])]
+    for t, blk in enumerate(model.blocks):
+        lins += [(f'si1{t}', f'{t}_self_interaction_1', model.irreps[t]),
+                 (f'si2{t}', f'{t}_self_interaction_2', blk['sc_irreps'][1])]
+    out = {}
+    for key, name, irreps in lins:
+        pname = f'{name}.linear.bias'
+        if pname not in model.slices:
+            continue
+        k = _zero_e_prefix(irreps)
+        if k is None or k != model.slices[pname][1]:
+            return None
+        out[key] = (pname, k)
+    return out
+
+
+FCN_ACTS = ('relu', 'silu', 'tanh', 'sigmoid', 'abs', 'elu')    # csrc/fcn_act.h's kinds
+FCN_MAX_HIDDEN, FCN_MAX_WIDTH = 4, 128                          # csrc/node.h
+
+
+def _fcn_spec(model):
+    """(widths [D, hidden...], activation name, act_norm) of an FCN readout
+    within the kernels' limits, else None"""
+    ro = model.readout_cfg
+    hidden = list(ro.get('hidden') or [])
+    if ro.get('type') != 'fcn' or ro.get('act') not in FCN_ACTS or 'act_norm' not in ro:
+        return None
+    if any(l != 0 or p != 1 for _, l, p in model.irreps[-1]):
+        return None
+    widths = [sum(m for m, _, _ in model.irreps[-1])] + hidden
+    if not 1 <= len(hidden) <= FCN_MAX_HIDDEN or \
+            any(int(w) != w or not 1 <= w <= FCN_MAX_WIDTH for w in widths):
+        return None
+    return [int(w) for w in widths], ro['act'], float(ro['act_norm'])
+
+
+def fcn_act_derivs(act, z):
+    """(f, f', f'') of the FCN readout's activation (csrc/fcn_act.h)"""
+    if act == 'relu':
+        pos = (z > 0).to(z.dtype)
+        return z * pos, pos, torch.zeros_like(z)
+    if act == 'silu':
+        s = torch.sigmoid(z)
+        return z * s, s * (1 + z * (1 - s)), s * (1 - s) * (2 + z * (1 - 2 * s))
+    if act == 'tanh':
+        t = torch.tanh(z)
+        return t, 1 - t * t, -2 * t * (1 - t * t)
+    if act == 'sigmoid':
+        s = torch.sigmoid(z)
+        return s, s * (1 - s), s * (1 - s) * (1 - 2 * s)
+    if act == 'abs':
+        return z.abs(), torch.sign(z), torch.zeros_like(z)
+    if act == 'elu':
+        neg = z <= 0
+        ez = torch.exp(torch.where(neg, z, torch.zeros_like(z)))
+        one, zero = torch.ones_like(z), torch.zeros_like(z)
+        return torch.where(neg, ez - 1, z), torch.where(neg, ez, one), torch.where(neg, ez, zero)
+    raise ValueError(f'unknown FCN activation {act!r}')
+
+
+class _Fcn:
+    """The FCN readout (e3nn FullyConnectedNet, no biases) at first and second
+    order: z_k = a_{k-1} W_k, a_k = c f(z_k), s = a_nh . v with every W scaled
+    by 1/sqrt(fan_in) -- the three launches of csrc/fcn_train.hip for float32
+    device tensors, torch formulas of the same algebra otherwise.
+
+    A state dict carries what the later passes need, per hidden layer:
+    Z, ZD [n, w] (z_k, z'_k) and A, ZB [2n, w] stacked primal rows then tangent
+    rows ([a_k; a'_k], [z-bar_k; z'-bar_k]: the weight gradients' operands)."""
+
+    def __init__(self, widths, act, c, lib=None):
+        self.w = [int(w) for w in widths]
+        self.nh = len(self.w) - 1
+        self.act, self.kind, self.c = act, FCN_ACTS.index(act), float(c)
+        self.lib = lib
+        self.cw = (ctypes.c_int32 * len(self.w))(*self.w)
+        # the packed weights (csrc/node.h FcnDims): matrix k row-major with
+        # the odd row stride w[k + 1] | 1, then v, padded to a multiple of 4
+        self.strides = [self.w[k + 1] | 1 for k in range(self.nh)]
+        self.offs = np.concatenate([[0], np.cumsum([self.w[k] * self.strides[k]
+                                                    for k in range(self.nh)])]).astype(np.int64)
+        self.packed_floats = (int(self.offs[-1]) + self.w[-1] + 3) & ~3
+
+    def pack_map(self, starts):
+        """(idx, scl): packed[i] = flat[idx[i]] * scl[i], ``starts`` the flat
+        offsets of the nh + 1 layer weights (padding: scl 0)"""
+        idx = np.zeros(self.packed_floats, dtype=np.int64)
+        scl = np.zeros(self.packed_floats)
+        for k in range(self.nh + 1):
+            wi, wo = self.w[k], (self.w[k + 1] if k < self.nh else 1)
+            st = self.strides[k] if k < self.nh else 1
+            i, j = np.meshgrid(np.arange(wi), np.arange(wo), indexing='ij')
+            pos = (int(self.offs[k]) + i * st + j).ravel()
+            idx[pos] = (starts[k] + i * wo + j).ravel()
+            scl[pos] = 1.0 / math.sqrt(wi)
+        return idx, scl
+
+    def pack(self, Ws):
+        """the packed buffer of the (scaled) matrices Ws (tests)"""
+        idx, scl = self.pack_map(np.concatenate([[0], np.cumsum([W.numel() for W in Ws])])[:-1])
+        flat = torch.cat([W.reshape(-1) for W in Ws])
+        return flat[torch.as_tensor(idx, device=flat.device)] * \
+            torch.as_tensor(scl != 0, device=flat.device, dtype=flat.dtype)
+
+    def _hip(self, x):
+        return self.lib is not None and x.is_cuda and x.dtype == torch.float32
+
+    def _args(self, n, packed):
+        return (n, self.nh, self.cw, self.kind, ctypes.c_float(self.c), packed.data_ptr())
+
+    @staticmethod
+    def _stream(t):
+        return torch.cuda.current_stream(t.device).cuda_stream
+
+    def _layers(self, buf, n, rows):
+        out, pre = [], 0
+        for w in self.w[1:]:
+            out.append(buf[rows * n * pre:rows * n * (pre + w)].view(rows * n, w))
+            pre += w
+        return out
+
+    def forward(self, x, Ws, packed, seed=None, need_dx=True):
+        """x [n, D] -> the state with s [n] and dx [n, D] = seed ds/dx"""
+        n, tot = int(x.shape[0]), sum(self.w[1:])
+        new = lambda *shape: torch.empty(*shape, device=x.device, dtype=x.dtype)   # noqa: E731
+        st = {'n': n, 'Ws': Ws, 'packed': packed, 's': new(n), 'dx': new(n, self.w[0]) if need_dx else None}
+        if self._hip(x):
+            from . import _lib
+            zbuf, zdbuf, abuf, zbbuf = new(n * tot), new(n * tot), new(2 * n * tot), new(2 * n * tot)
+            st.update(Z=self._layers(zbuf, n, 1), ZD=self._layers(zdbuf, n, 1), A=self._layers(abuf, n, 2),
+                      ZB=self._layers(zbbuf, n, 2), bufs=(zbuf, zdbuf, abuf, zbbuf))
+            x = x.contiguous()
+            ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+            _lib.check(self.lib.e3gnn_fcn_train_forward(
+                *self._args(n, packed), x.data_ptr(), ptr(seed.contiguous() if seed is not None else None),
+                zbuf.data_ptr(), abuf.data_ptr(), st['s'].data_ptr(), ptr(st['dx']), self._stream(x)))
+            return st
+        st.update(Z=[], ZD=[None] * self.nh, A=[new(2 * n, w) for w in self.w[1:]],
+                  ZB=[new(2 * n, w) for w in self.w[1:]])
+        a = x
+        for k in range(self.nh):
+            z = a @ Ws[k]
+            a = self.c * fcn_act_derivs(self.act, z)[0]
+            st['Z'].append(z)
+            st['A'][k][:n] = a
+        st['s'].copy_((a @ Ws[self.nh])[:, 0])
+        if need_dx:
+            g = self.c * fcn_act_derivs(self.act, st['Z'][-1])[1] * Ws[self.nh][:, 0]
+            for k in range(self.nh - 1, 0, -1):
+                g = (g @ Ws[k].t()) * (self.c * fcn_act_derivs(self.act, st['Z'][k - 1])[1])
+            g = g @ Ws[0].t()
+            st['dx'].copy_(g if seed is None else g * seed.unsqueeze(-1))
+        return st
+
+    def tangent(self, st, xd):
+        """x' [n, D] -> s' [n] (and z'_k, a'_k into the state)"""
+        n = st['n']
+        sd = torch.empty(n, device=xd.device, dtype=xd.dtype)
+        if self._hip(xd):
+            from . import _lib
+            zbuf, zdbuf, abuf, _ = st['bufs']
+            _lib.check(self.lib.e3gnn_fcn_train_tangent(
+                *self._args(n, st['packed']), xd.contiguous().data_ptr(), zbuf.data_ptr(), zdbuf.data_ptr(),
+                abuf.data_ptr(), sd.data_ptr(), self._stream(xd)))
+            return sd
+        Ws, ad = st['Ws'], xd
+        for k in range(self.nh):
+            zd = ad @ Ws[k]
+            ad = self.c * fcn_act_derivs(self.act, st['Z'][k])[1] * zd
+            st['ZD'][k] = zd
+            st['A'][k][n:] = ad
+        sd.copy_((ad @ Ws[self.nh])[:, 0])
+        return sd
+
+    def dual(self, st, sb, sbd):
+        """the reverse of (s, s') seeded with (sb, sbd): [x-bar; x'-bar]
+        [2n, D] (and [z-bar_k; z'-bar_k] into the state)"""
+        n = st['n']
+        XB = torch.empty(2 * n, self.w[0], device=sb.device, dtype=sb.dtype)
+        if self._hip(sb):
+            from . import _lib
+            zbuf, zdbuf, _, zbbuf = st['bufs']
+            _lib.check(self.lib.e3gnn_fcn_train_dual(
+                *self._args(n, st['packed']), sb.contiguous().data_ptr(), sbd.contiguous().data_ptr(),
+                zbuf.data_ptr(), zdbuf.data_ptr(), zbbuf.data_ptr(), XB.data_ptr(), self._stream(sb)))
+            return XB
+        Ws = st['Ws']
+        v = Ws[self.nh][:, 0]
+        ab, abd = sb.unsqueeze(-1) * v, sbd.unsqueeze(-1) * v
+        for k in range(self.nh - 1, -1, -1):
+            _, d1, d2 = fcn_act_derivs(self.act, st['Z'][k])
+            zbd = self.c * d1 * abd
+            zbp = self.c * d1 * ab + self.c * d2 * st['ZD'][k] * abd
+            st['ZB'][k][:n] = zbp
+            st['ZB'][k][n:] = zbd
+            ab, abd = zbp @ Ws[k].t(), zbd @ Ws[k].t()
+        XB[:n] = ab
+        XB[n:] = abd
+        return XB
 
 
 # ------------------------------------------------------------------ primitives
@@ -767,19 +996,26 @@ class ExplicitStep:
 
     def __init__(self, model):
         if not supported(model):
-            raise ValueError('the explicit fine-tune derivatives cover SevenNet-0\'s architecture only')
+            raise ValueError('the explicit fine-tune derivatives cover SevenNet-0\'s architecture only '
+                             '(with or without linear biases; the linear readout or an FCN readout '
+                             'of 1-4 hidden layers of 1-128 units)')
         self.m = model
         self.p = _Prims(model)
         self.gm = _Gemms(model)
         self.geo = _Geometry(model, self.p)
         self.gates = [_Gate(b['gate'], self.p) for b in model.blocks]
+        # key -> (bias parameter, its leading 0e columns); the FCN readout
+        self.biases = _bias_map(model)
+        spec = _fcn_spec(model) if model.readout_cfg.get('type', 'linear') != 'linear' else None
+        self.fcn = _Fcn(*spec, lib=self.p.lib) if spec is not None else None
         ent = []
         for t, blk in enumerate(model.blocks):
             ent += [(f'sc{t}', blk['sc'], f'{t}_self_connection_intro.linear.weight'),
                     (f'si1{t}', blk['si1'], f'{t}_self_interaction_1.linear.weight'),
                     (f'si2{t}', blk['si2'], f'{t}_self_interaction_2.linear.weight')]
-        ent += [('r1', model.readout1, 'reduce_input_to_hidden.linear.weight'),
-                ('r2', model.readout2, 'reduce_hidden_to_energy.linear.weight')]
+        if self.fcn is None:
+            ent += [('r1', model.readout1, 'reduce_input_to_hidden.linear.weight'),
+                    ('r2', model.readout2, 'reduce_hidden_to_energy.linear.weight')]
         # frozen convolution denominators (the default) are folded into si2:
         # agg / den W = agg (W / den), and the si2 gradient divided by den in
         # the flush -- no division launches on the activations
@@ -806,7 +1042,26 @@ class ExplicitStep:
                 views.append((off, shape))
                 off += cnt
             self.mlp_views.append(views)
+        # ... and the FCN readout's matrices, scaled likewise, in the packed
+        # layout of its kernels (torch path: plain views beside them)
+        self.fcn_names, self.fcn_packed, self.fcn_views = [], None, []
+        if self.fcn is not None:
+            self.fcn_names = [f'readout_FCN.fcn.layer{k}.weight' for k in range(self.fcn.nh + 1)]
+            sl = [model.slices[nm] for nm in self.fcn_names]
+            if self.p.lib is not None and model.flat.dtype == torch.float32:
+                pidx, pscl = self.fcn.pack_map([s[0] for s in sl])
+                idx.append(pidx)
+                scl.append(pscl)
+                self.fcn_packed = (off, self.fcn.packed_floats)
+                off += self.fcn.packed_floats
+            else:
+                for o, cnt, shape in sl:
+                    idx.append(np.arange(o, o + cnt))
+                    scl.append(np.full(cnt, 1.0 / math.sqrt(shape[0])))
+                    self.fcn_views.append((off, shape))
+                    off += cnt
         dev, dt = model.flat.device, model.flat.dtype
+        self._one = torch.ones(1, device=dev, dtype=dt)   # the ones column of a bias pair
         self.mlp_idx = torch.as_tensor(np.concatenate(idx), device=dev)
         self.mlp_scl = torch.as_tensor(np.concatenate(scl), device=dev, dtype=dt)
         self.mlp_buf = torch.empty(off, device=dev, dtype=dt)
@@ -842,6 +1097,56 @@ class ExplicitStep:
                                                              self._stream(self.mlp_buf)))
             self._w2p_of = {W[2].data_ptr(): q for W, q in zip(Ws, self.w2p)}
         return Ws
+
+    def _fcn_weights(self):
+        """(scaled matrices, packed buffer) of the FCN readout out of the
+        buffer _mlp_weights filled: the packed image for its kernels, or the
+        matrices for the torch formulas"""
+        if self.fcn_packed is not None:
+            o, cnt = self.fcn_packed
+            return None, self.mlp_buf[o:o + cnt]
+        return [self.mlp_buf[o:o + int(np.prod(sh))].view(*sh) for o, sh in self.fcn_views], None
+
+    # ---- linear biases (use_bias_in_linear): y = x W + b on the PRIMAL rows
+    # only (b does not depend on the edge vectors: y' = x' W), and dL/db = the
+    # column sum of the primal cotangent over the biased (leading 0e) columns
+    def _add_bias(self, key, Y):
+        if key in self.biases:
+            name, k = self.biases[key]
+            Y[:, :k].add_(self._P(name).detach())
+
+    def _bias_pair(self, key, n):
+        """key's bias as the second operand pair of a product whose whole
+        output row is biased: ones [n, 1] (one element, row stride 0) x b [1, k]
+        -- the add rides in the product's launch"""
+        if key not in self.biases:
+            return {}
+        name, k = self.biases[key]
+        return dict(A2=self._one.expand(n, 1), B2=self._P(name).detach().view(1, k))
+
+    def _bias_cot(self, key, C):
+        """C: the primal cotangent rows that meet key's biased output (kept
+        alive until _bias_grads sums every bias's in one launch)"""
+        if key in self.biases and self._P(self.biases[key][0]).requires_grad:
+            self._bcot.append((self.biases[key], C))
+
+    def _bias_grads(self):
+        pend, self._bcot = self._bcot, []
+        if not pend:
+            return
+        if not all(self.p._hip(C) for _, C in pend):
+            for (name, k), C in pend:
+                self._G(name).add_(C[:, :k].sum(0))
+            return
+        from . import _lib
+        for i in range(0, len(pend), 16):
+            part = pend[i:i + 16]
+            descs = (_lib.ColsumDesc * len(part))()
+            for d, ((name, k), C) in zip(descs, part):
+                assert C.stride(1) == 1
+                d.src, d.dst, d.ld = C.data_ptr(), self._G(name).data_ptr(), C.stride(0)
+                d.rows, d.cols = int(C.shape[0]), k
+            _lib.check(self.p.lib.e3gnn_colsum_grouped(len(part), descs, self._stream(pend[0][1])))
 
     def _P(self, name):
         return self.m.param(name)
@@ -885,18 +1190,24 @@ class ExplicitStep:
     def _irr(self, *ts):
         return self._irreps and self.gm._hip(*ts)
 
-    def _lin(self, C, A, key, A2=None, key2=None, trans=False, beta=0, flush=True):
+    def _lin(self, C, A, key, A2=None, key2=None, trans=False, beta=0, flush=True, bias=None):
         """C = A op(D[key]) [+ A2 op(D[key2])], op = identity or transpose, one
         problem per l-block (the dense product with its zero-block ranges on
-        other devices / dtypes)"""
+        other devices / dtypes).  bias: + that key's bias on C's leading 0e
+        columns (C: primal rows, flush) -- as a K = 1 second operand pair of
+        the l = 0 problem where that pair is free, else an add of its own"""
         D = self.S['D']
+        if bias is not None and bias not in self.biases:
+            bias = None
         if not self._irr(C, A, *([A2] if A2 is not None else [])):
             B = D[key].t() if trans else D[key]
             B2 = None if key2 is None else (D[key2].t() if trans else D[key2])
             kr = self._kr((key, trans), None if key2 is None else (key2, trans))
             self.gm.add(C, A, B, beta=beta, A2=A2, B2=B2, kr=kr)
-            if flush:
+            if flush or bias is not None:
                 self.gm.flush()
+            if bias is not None:
+                self._add_bias(bias, C)
             return C
         from . import _lib
         rows = int(A.shape[0])
@@ -919,13 +1230,22 @@ class ExplicitStep:
                 La.ld, La.rep, La.rs, La.kst, La.ks, La.sst = Ai.stride(0), d, 1, d, K, 0
                 Lb.ld, Lb.rep, Lb.rs, Lb.kst, Lb.ks, Lb.sst = b_ld, 1, 0, b_kst, K, 0
                 ops.append(((Ai, a_lo), (Dk, b_off), K))
+            if bias is not None and l == 0 and len(ps) == 1 and c_lo == 0 and N == self.biases[bias][1]:
+                # + 1 b: every row reads the one element of the ones column
+                La, Lb = lay.a2, lay.b2
+                La.ld, La.rep, La.rs, La.kst, La.ks, La.sst = 0, 1, 0, 1, 1, 0
+                Lb.ld, Lb.rep, Lb.rs, Lb.kst, Lb.ks, Lb.sst = 1, 1, 0, 1, 1, 0
+                ops.append(((self._one, 0), (self._P(self.biases[bias][0]).detach(), 0), 1))
+                bias = None
             lay.ldc, lay.crep, lay.crs, lay.cns = C.stride(0), d, 1, d
             extra = {}
             if len(ops) > 1:
                 extra = dict(A2=ops[1][0], B2=ops[1][1], K2=ops[1][2])
             self.gm.add_lay(rows * d, N, ops[0][2], (C, c_lo), ops[0][0], ops[0][1], lay, beta=beta, **extra)
-        if flush:
+        if flush or bias is not None:
             self.gm.flush()
+        if bias is not None:                    # (both pairs taken: si2 + sc)
+            self._add_bias(bias, C)
         return C
 
     def _lin_grad(self, G, X, Y, key):
@@ -1123,7 +1443,13 @@ class ExplicitStep:
         P = lambda name: self._P(name).detach()   # noqa: E731
         emb_w = P('onehot_to_feature_x.linear.weight').view(m.nsp, -1)
         X = torch.empty(2 * n, emb_w.shape[1], device=dev, dtype=dt)
-        torch.mul(emb_w[types], 1.0 / math.sqrt(m.nsp), out=X[:n])
+        if self.biases.get('emb', (None, 0))[1] == emb_w.shape[1]:
+            # the species table scaled and biased (one launch), then gathered
+            tab = torch.add(P(self.biases['emb'][0]), emb_w, alpha=1.0 / math.sqrt(m.nsp))
+            torch.index_select(tab, 0, types, out=X[:n])
+        else:
+            torch.mul(emb_w[types], 1.0 / math.sqrt(m.nsp), out=X[:n])
+            self._add_bias('emb', X[:n])
         X[n:].zero_()                          # x0 does not depend on the edge vectors
         blocks = []
         be = m.conv_backend
@@ -1133,7 +1459,7 @@ class ExplicitStep:
             W0, W1, W2 = MW[t]
             x = X[:n]
             H = new(2 * n, D[f'si1{t}'].shape[1])
-            self._lin(H[:n], x, f'si1{t}')
+            self._lin(H[:n], x, f'si1{t}', bias=f'si1{t}')
             A1, H1 = new(2 * E, W0.shape[1]), new(2 * E, W0.shape[1])
             A2, H2 = new(2 * E, W1.shape[1]), new(2 * E, W1.shape[1])
             WT = new(2 * E, W2.shape[1])
@@ -1144,24 +1470,33 @@ class ExplicitStep:
             if not self.fold_den:            # (folded: D[si2] is si2 / den)
                 AGG[:n].div_(den)
             Yg = new(2 * n, D[f'si2{t}'].shape[1])
-            self._lin(Yg[:n], x, f'sc{t}', A2=AGG[:n], key2=f'si2{t}')   # x sc + agg si2: one product
-            Xn = new(2 * n, self.gates[t].dims[3] if self.gates[t].ng else Yg.shape[1])
+            # x sc + agg si2: one product; si2's bias (not divided by a folded denominator)
+            self._lin(Yg[:n], x, f'sc{t}', A2=AGG[:n], key2=f'si2{t}', bias=f'si2{t}')
+            Xn =new(2 * n, self.gates[t].dims[3] if self.gates[t].ng else Yg.shape[1])
             self.gates[t].fwd(Yg[:n], out=Xn[:n])
             blocks.append({'X': X, 'H': H, 'A1': A1, 'H1': H1, 'A2': A2, 'H2': H2, 'WT': WT,
                            'W': (W0, W1, W2), 'den': den, 'AGG': AGG, 'Y': Yg})
             X = Xn
         S['blocks'] = blocks
         S['XL'] = X
-        hid = self._mm(new(n, D['r1'].shape[1]), X[:n], D['r1'])
-        e = self._mm(new(n, 1), hid, D['r2'])[:, 0]
         scale = P('rescale_atomic_energy.scale')[types]
+        if self.fcn is not None:
+            # the FCN readout and its first reverse, one launch: e and
+            # x-bar = scale de/dx (seed dE/d atomic = 1)
+            S['fcn'] = self.fcn.forward(X[:n], *self._fcn_weights(), seed=scale)
+            hid, e, xb = None, S['fcn']['s'], S['fcn']['dx']
+        else:
+            # (the readout linears' biases: second operand pairs of their products)
+            hid = self._mm(new(n, D['r1'].shape[1]), X[:n], D['r1'], **self._bias_pair('r1', n))
+            e = self._mm(new(n, 1), hid, D['r2'], **self._bias_pair('r2', n))[:, 0]
         atomic = e * scale + P('rescale_atomic_energy.shift')[types]
         S.update(hid=hid, e=e, scale=scale)
         energy = torch.zeros(nb, device=dev, dtype=atomic.dtype).index_add(0, batch, atomic)
 
         # ---- first reverse: dE/dr per edge (seed dE/d atomic = 1)
-        xb = self._mm(new(n, D['r1'].shape[0]), scale.unsqueeze(-1) * D['r2'][:, 0].unsqueeze(0),
-                      D['r1'].t())
+        if self.fcn is None:
+            xb = self._mm(new(n, D['r1'].shape[0]), scale.unsqueeze(-1) * D['r2'][:, 0].unsqueeze(0),
+                          D['r1'].t())
         Yb = torch.empty_like(g['Y'])         # the last block's launch assigns, the others add
         embb = torch.zeros_like(g['emb'])
         for t in range(len(blocks) - 1, -1, -1):
@@ -1250,8 +1585,11 @@ class ExplicitStep:
             Xn = blocks[t + 1]['X'] if t + 1 < len(blocks) else S['XL']
             self.gates[t].jvp(Yg[:n], Yg[n:], out=Xn[n:])
         XL = S['XL']
-        hidd = self._mm(torch.empty(n, D['r1'].shape[1], device=dev, dtype=dt), XL[n:], D['r1'])
-        ed = self._mm(torch.empty(n, 1, device=dev, dtype=dt), hidd, D['r2'])[:, 0]
+        if self.fcn is not None:
+            ed = self.fcn.tangent(S['fcn'], XL[n:])
+        else:
+            hidd = self._mm(torch.empty(n, D['r1'].shape[1], device=dev, dtype=dt), XL[n:], D['r1'])
+            ed = self._mm(torch.empty(n, 1, device=dev, dtype=dt), hidd, D['r2'])[:, 0]
 
         # ---- one reverse sweep over (primal, tangent); seeds cE on E, 1 on E'
         G = self.bank.grads()
@@ -1268,12 +1606,26 @@ class ExplicitStep:
             gsh.index_add_(0, types, atb)
         # [e-bar; e'-bar] = [cE scale; scale]
         EB = torch.cat([atb * scale, scale]).unsqueeze(-1)
-        HID = torch.cat([S['hid'], hidd])
-        HIDB = EB * D['r2'][:, 0].unsqueeze(0)
-        XB = torch.empty(2 * n, D['r1'].shape[0], device=dev, dtype=dt)
-        self.gm.add(G['r2'], HID.t(), EB, beta=1, wgrad=True)
-        self.gm.add(G['r1'], XL.t(), HIDB, beta=1, wgrad=True)
-        self.gm.add(XB, HIDB, D['r1'].t())    # [x-bar; x'-bar] of the last block's output
+        self._bcot = []
+        if self.fcn is not None:
+            # the dual reverse of the FCN readout, one launch; its weight
+            # gradients [a; a']^T [z-bar; z'-bar] / sqrt(fan_in) with the sweep's
+            fs, w = S['fcn'], self.fcn.w
+            XB = self.fcn.dual(fs, EB[:n, 0], EB[n:, 0])
+            ins = [XL] + fs['A']
+            for k, (name, cot) in enumerate(zip(self.fcn_names, fs['ZB'] + [EB])):
+                gw = self._G(name)
+                if gw is not None:
+                    self.gm.add(gw, ins[k].t(), cot, 1.0 / math.sqrt(w[k]), beta=1, wgrad=True)
+        else:
+            HID = torch.cat([S['hid'], hidd])
+            HIDB = EB * D['r2'][:, 0].unsqueeze(0)
+            XB = torch.empty(2 * n, D['r1'].shape[0], device=dev, dtype=dt)
+            self.gm.add(G['r2'], HID.t(), EB, beta=1, wgrad=True)
+            self.gm.add(G['r1'], XL.t(), HIDB, beta=1, wgrad=True)
+            self.gm.add(XB, HIDB, D['r1'].t())    # [x-bar; x'-bar] of the last block's output
+            self._bias_cot('r2', EB[:n])
+            self._bias_cot('r1', HIDB[:n])
         self.gm.flush()
         EMBB = torch.zeros(2 * E, 8, device=dev, dtype=dt)
         new = lambda *shape: torch.empty(*shape, device=dev, dtype=dt)   # noqa: E731
@@ -1285,6 +1637,7 @@ class ExplicitStep:
             Yg, AGG, X, H = b['Y'], b['AGG'], b['X'], b['H']
             YB = new(2 * n, Yg.shape[1])
             self.gates[t].dual_vjp(Yg[:n], Yg[n:], XB[:n], XB[n:], out0=YB[:n], out1=YB[n:])
+            self._bias_cot(f'si2{t}', YB[:n])
             # independent products of y-bar, one launch: si2's and sc's weight
             # gradients and agg-bar
             AGGB = new(2 * n, D[f'si2{t}'].shape[0])
@@ -1331,6 +1684,7 @@ class ExplicitStep:
                     self.gm.add(gw, rows.t(), cot, 1.0 / math.sqrt(Wl.shape[0]), beta=1, wgrad=True)
             # self-interaction 1 (sc-bar = y-bar, added above) and the input cotangent
             self._lin_grad(G[f'si1{t}'], X, HB, f'si1{t}')
+            self._bias_cot(f'si1{t}', HB[:n])
             XB = new(2 * n, D[f'si1{t}'].shape[0])
             self._lin(XB, HB, f'si1{t}', A2=YB, key2=f'sc{t}', trans=True, flush=False)
             self.gm.flush()
@@ -1342,5 +1696,7 @@ class ExplicitStep:
         if gco is not None:
             coeffs = self._P('edge_embedding.basis_function.coeffs').detach()
             gco.add_(self.geo.coeff_grad(g, EMBB[:E], EMBB[E:], rd, coeffs))
+        self._bias_cot('emb', XB[:n])
+        self._bias_grads()                    # every bias gradient, one launch
         self.gm.finish_defer()
         self.bank.flush(m.flat_grad)
