@@ -1253,7 +1253,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // and needs no per-wave prefetch registers.  The backward's dH2 = dw W2^T runs
 // on bf16x6 MFMA over the pair (K = 32 channels): 24 x 16 MFMA cycles instead of
 // 2 x 16 x 32 on f32 MFMA.  Middle blocks: two workgroups per CU (LDS), 2 waves
-// per SIMD; the first block: 3 waves per SIMD.
+// per SIMD (SevenNet-0's: two pairs per barrier, LsQuads); the first block: 3
+// waves per SIMD.
 
 // The pair's W2 pieces are staged ONCE, as the [hidden][channel] image of
 // w2_image.h (MlpW::w2s): dH2 reads it by rows, the w recompute transposed
@@ -1345,7 +1346,8 @@ __device__ __forceinline__ int ls_tiles(const int* __restrict__ row_ptr, int cb,
 // waves per SIMD: the first block (128 input channels, 1,152 message channels:
 // 34.8 KB of LDS per workgroup, two images) runs three (168 VGPRs with a few
 // spills measured 2.57 -> 2.27 ms against two), the middle blocks two (their
-// 230 VGPRs allow no more; 64.5 KB of LDS per workgroup)
+// 230-243 VGPRs allow no more; 64.5 KB of LDS per workgroup, 80.9 KB with
+// two pairs per barrier, LsQuads below)
 template <class L>
 struct BwdLsWaves {
   static constexpr int v = L::KIND == 0 ? 3 : 2;
@@ -1363,10 +1365,9 @@ constexpr int LS_WPG = 4;
 // builds); in the middle blocks the 0e x 0e -> 0e path's dE/dagg (C0 floats,
 // moff 0) is read from L2 with the neighbour-row prefetch instead of staged (a
 // choice made when the pair was staged as two 16 KB images and two workgroups
-// would not otherwise fit a CU; SevenNet-0's middle block is now 2 x 64.5 KB
-// of 160 KB, and staging the slice again measured no gain: DESIGN.md 8 item
-// 1).  Where two images do not fit: one image, written between two
-// barriers per pair.  Writing the images by LDS-DMA straight from L2 was
+// would not otherwise fit a CU, as again with LsQuads' four images; staging
+// the slice again measured no gain without them: DESIGN.md 8 item 1).  Where
+// two images do not fit: one image, written between two barriers per pair.  Writing the images by LDS-DMA straight from L2 was
 // measured and rejected (5.68 -> 5.77 ms: its explicit wait before the barrier
 // drains every load and store in flight).
 template <class L>
@@ -1375,6 +1376,29 @@ struct LsTwoImages {
   static constexpr int DMS = L::DM - OFF0;                       // staged dE/dagg floats per centre
   static constexpr int bytes = LS_WPG * DMS * 4 + 2 * LS_IMG;
   static constexpr bool v = BwdLsWaves<L>::v * bytes <= 163840;
+};
+// Two pairs per barrier: each of the two buffers holds the images of two
+// consecutive pairs (a group of four blocks), written and published at the
+// group's start, so a tile runs half the barriers.  It needs every block's
+// position in its group of four to be a compile-time constant (the channel
+// groups of an input irrep unrolled until their blocks are a multiple of four)
+// and 4 images beside the staged rows at the kernel's workgroups per CU:
+// SevenNet-0's middle block (80,896 B, two per CU); c64's rows are too long,
+// c32's l1 = 0 groups too few.  Step 37.64-38.06 -> 37.23-37.37 ms, launch 5.12 ->
+// 4.87 ms against one pair per barrier (profiles/quads_bench.log).  The same kernel at THREE waves
+// per SIMD (the l1 = 0 paths' dE/dagg from L2, 50.4 KB of LDS, 168 VGPRs) was
+// measured first and ran no faster than at two: DESIGN.md 8 item 1.
+template <class L>
+struct LsQuads {
+  static constexpr int unroll(int npi) { return npi % 4 == 0 ? 1 : npi % 2 == 0 ? 2 : 4; }
+  static constexpr bool pos_ok() {
+    if (L::W / 16 % 4) return false;
+    for (int i = 0; i < 3; ++i)
+      if (mul_of<L>(i) > 0 && (mul_of<L>(i) / 16 % unroll(paths_of<L>(i)) || blocks_before<L>(i) % 4)) return false;
+    return true;
+  }
+  static constexpr int bytes = LS_WPG * (L::DM - LsTwoImages<L>::OFF0) * 4 + 4 * LS_IMG;
+  static constexpr bool v = L::KIND == 1 && LsTwoImages<L>::v && pos_ok() && BwdLsWaves<L>::v * bytes <= 163840;
 };
 // wave priority, raised around the lock-step backward's MFMA bursts
 template <int P>
@@ -1393,13 +1417,15 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
   constexpr int NST = LS_IMG / 16 / NT;
   static_assert(LS_IMG / 16 % NT == 0, "staging pieces per thread");
   constexpr bool TWO = LsTwoImages<L>::v;   // two images, one barrier per pair
+  constexpr bool QUAD = LsQuads<L>::v;      // two pairs per image and barrier
+  constexpr int NIMG = QUAD ? 2 : 1;        // pairs staged at a time
   // tile-start values kept in registers to the tile end (the first block at
   // three waves per SIMD: no VGPRs to spare)
   constexpr bool KEEP = BwdLsWaves<L>::v == 2;
   constexpr int OFF0 = TWO ? LsTwoImages<L>::OFF0 : 0, DMS = L::DM - OFF0;   // dE/dagg floats staged per centre
   static_assert(!TWO || (L::P[0].l1 == 0 && L::P[0].l2 == 0 && L::P[0].l3 == 0 && L::P[0].moff == 0 &&
                          OFF0 % 4 == 0), "path 0 is the 0e x 0e -> 0e slice at the row start");
-  __shared__ __attribute__((aligned(16))) float smem[WPG * DMS + (TWO ? 2 : 1) * LS_IMG / 4];
+  __shared__ __attribute__((aligned(16))) float smem[WPG * DMS + (TWO ? 2 : 1) * NIMG * LS_IMG / 4];
   const int tid = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, g = lane >> 4, col = lane & 15;
   const int cb = c_begin + blockIdx.x * WPG;
   const int c = cb + wid;
@@ -1421,10 +1447,11 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
   const WRes R = make_wres(W, L::W);
   const __amdgpu_buffer_rsrc_t Rs = rsrc_bytes(W.w2s, NPAIR * w2img::PAIR_BYTES);   // the pair images
   const __amdgpu_buffer_rsrc_t Rx = rsrc_bytes(h, (int64_t)n_nodes * L::DX * 4);
-  f32x4 st[NST];
-  auto issue = [&](int P) {
+  f32x4 st[NIMG * NST];
+  auto issue = [&](int P) {   // pairs P .. P + NIMG - 1
 #pragma unroll
-    for (int i = 0; i < NST; ++i) st[i] = ldw4(Rs, (tid + NT * i) * 16, P * w2img::PAIR_BYTES);
+    for (int i = 0; i < NIMG * NST; ++i)
+      st[i] = ldw4(Rs, (tid + NT * (i % NST)) * 16, (P + i / NST) * w2img::PAIR_BYTES);
   };
   // the single image: the previous pair's reads retired, the pair written, published
   auto commit = [&]() {
@@ -1514,11 +1541,13 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
         constexpr int D1 = 2 * I + 1;
         constexpr int XOFF = iblock_xoff<L, I>();
         // an odd number of paths: two channel groups per iteration, so the
-        // position of every block in its pair is a compile-time constant (no
-        // branches around the staging: the wait counts stay exact)
-        constexpr int NPI = paths_of<L>(I), U = (NPI & 1) ? 2 : 1, NB0 = blocks_before<L>(I);
+        // position of every block in its pair (QUAD: in its group of four) is a
+        // compile-time constant (no branches around the staging: the wait
+        // counts stay exact)
+        constexpr int NPI = paths_of<L>(I), NB0 = blocks_before<L>(I);
+        constexpr int U = QUAD ? LsQuads<L>::unroll(NPI) : (NPI & 1) ? 2 : 1;
         static_assert((MUL / 16) % U == 0, "channel groups come in pairs");
-        for (int j2 = 0; j2 < MUL / 16; j2 += U) {
+        auto groups = [&](const int j2) {
           sfor<U>([&](auto hh) {
             const int jj = j2 + hh;
             float x[4 * D1], dx[4 * D1], g0[4];
@@ -1541,18 +1570,19 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
               constexpr PathDef p = L::P[pi];
               if constexpr (p.l1 == I) {
                 constexpr int D3 = 2 * p.l3 + 1;
-                constexpr int ODD = (NB0 + hh * NPI + path_rank<L>(pi)) & 1;
+                constexpr int POS = (NB0 + hh * NPI + path_rank<L>(pi)) & (2 * NIMG - 1), ODD = POS & 1;
                 const int nb = NB0 + jj * NPI + path_rank<L>(pi);
-                const char* pimg = img + (TWO ? rb * LS_IMG : 0);   // this pair's image
-                if constexpr (!ODD) {   // pair start: stage it, fetch the next one
+                // this pair's image (QUAD: the first or second of its buffer)
+                const char* pimg = img + (TWO ? rb * NIMG * LS_IMG : 0) + (POS >> 1) * LS_IMG;
+                if constexpr (POS == 0) {   // pair (QUAD: two pairs) start: stage, fetch the next
                   if constexpr (STAMPED) STAMP(5);
-                  const int nextP = (nb >> 1) + 1 < NPAIR ? (nb >> 1) + 1 : 0;
+                  const int nextP = (nb >> 1) + NIMG < NPAIR ? (nb >> 1) + NIMG : 0;
                   if constexpr (TWO) {
                     // this pair's image (the one two pairs back read, retired
                     // by the previous pair's barrier), then the one barrier
 #pragma unroll
-                    for (int i = 0; i < NST; ++i)
-                      *reinterpret_cast<f32x4*>(img + rb * LS_IMG + (tid + NT * i) * 16) = st[i];
+                    for (int i = 0; i < NIMG * NST; ++i)
+                      *reinterpret_cast<f32x4*>(img + (rb * NIMG + i / NST) * LS_IMG + (tid + NT * (i % NST)) * 16) = st[i];
                     __syncthreads();
                     issue(nextP);
                   } else {
@@ -1560,6 +1590,8 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
                     issue(nextP);
                   }
                   if constexpr (STAMPED) STAMP(2);   // barriers + staging
+                }
+                if constexpr (!ODD) {
                   if (act) {
                     ls_prio<1>();   // MFMA bursts first
                     Op3 wq, wq1;   // both blocks' pieces read first
@@ -1599,7 +1631,7 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
                     for (int r = 0; r < 4; ++r) dwp[r] = dwr[r];
                   }
                 }
-                if constexpr (TWO && ODD) rb ^= 1;   // the next pair reads the other image
+                if constexpr (TWO && POS == 2 * NIMG - 1) rb ^= 1;   // the next pair(s) read the other buffer
               }
             });
             // per-edge dE/dx[nbr]; the first block's inputs are the species
@@ -1609,6 +1641,14 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
             if constexpr (L::KIND != 0)
               stv<4 * D1>(Rd, vd + 4 * g * D1 * 4, (XOFF + 16 * jj * D1) * 4, dx);
           });
+        };
+        if constexpr (QUAD) {
+          // every group unrolled (two passes at most): with a loop left, the
+          // branch around the prefetch kept three of its registers in scratch
+          // memory, and each of those accesses waits for every load in flight
+          sfor<MUL / 16 / U>([&](auto it) { groups(it * U); });
+        } else {
+          for (int j2 = 0; j2 < MUL / 16; j2 += U) groups(j2);
         }
       }
     });
