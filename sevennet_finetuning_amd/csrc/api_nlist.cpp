@@ -1,0 +1,332 @@
+// The device neighbour list and rank graph behind the C ABI (include/e3gnn.h;
+// kernels in neighbor.hip).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/e3gnn.h"
+#include "api_util.h"
+#include "dbuf.h"
+#include "neighbor.h"
+
+using namespace e3gnn;
+
+extern "C" {
+
+// ------------------------------------------------------------ neighbour list
+struct e3gnn_nlist {
+  int device = 0;
+  int64_t n = 0, E = 0;
+  NlGeom G{};
+  const double* pos = nullptr;
+  bool built = false;
+  DBuf f0, bin, bin_count, bin_start, cursor, bin_atoms, deg, row_ptr, err;
+  // rank graph (e3gnn_nlist_rank_build): counts and the row maps it keeps
+  bool rank_built = false;
+  int64_t n_local = 0, n_ghost = 0;
+  int world = 0;
+  DBuf flag, fpos, centers, bflag, degrow, owned, gid, ghosts, lid, hist, hoff, recv, sc_sum,
+      sc_off;
+};
+
+e3gnn_nlist* e3gnn_nlist_create(int device) {
+  if (hipSetDevice(device) != hipSuccess) {
+    fail(E3GNN_ERR_HIP, "hipSetDevice failed");
+    return nullptr;
+  }
+  auto* h = new e3gnn_nlist;
+  h->device = device;
+  return h;
+}
+void e3gnn_nlist_free(e3gnn_nlist* h) { delete h; }
+
+namespace {
+// bins of width >= rc per dimension (heights h), at most ~4 per atom
+void nl_bins(NlGeom& G, const double h[3], double rc, int64_t n) {
+  for (int k = 0; k < 3; ++k) G.nb[k] = std::max(1, (int)std::floor(h[k] / rc));
+  while ((int64_t)G.nb[0] * G.nb[1] * G.nb[2] > 4 * n + 64) {
+    int k = 0;
+    for (int q = 1; q < 3; ++q)
+      if (G.nb[q] > G.nb[k]) k = q;
+    G.nb[k] = std::max(1, G.nb[k] / 2);
+  }
+  for (int k = 0; k < 3; ++k) G.R[k] = std::max(1, (int)std::ceil(rc * G.nb[k] / h[k]));
+}
+
+// The geometry of the box and the atoms binned (k_nl_bin, scan, k_nl_place):
+// the part e3gnn_nlist_build and e3gnn_nlist_rank_build share.  `all`: all
+// three dimensions periodic, else an isolated cluster.
+int nl_bin_atoms(e3gnn_nlist* h, int64_t n, const double* pos, const double* cell, bool all,
+                 double cutoff, hipStream_t s) {
+  HIPCHK(hipSetDevice(h->device));
+  h->built = false;
+  h->rank_built = false;
+  h->n = n;
+  h->pos = pos;
+  NlGeom& G = h->G;
+  G = NlGeom{};
+  G.rc2 = cutoff * cutoff;
+  G.periodic = all ? 1 : 0;
+  double hgt[3];
+  if (all) {
+    if (!cell) return fail(E3GNN_ERR_ARG, "null cell");
+    for (int k = 0; k < 9; ++k) G.cell[k] = cell[k];
+    const double* a = cell;
+    const double det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) +
+                       a[2] * (a[3] * a[7] - a[4] * a[6]);
+    if (!(std::fabs(det) > 1e-12)) return fail(E3GNN_ERR_ARG, "singular cell");
+    // inverse (rows of cell = lattice vectors): frac = pos @ inv
+    G.inv[0] = (a[4] * a[8] - a[5] * a[7]) / det;
+    G.inv[1] = (a[2] * a[7] - a[1] * a[8]) / det;
+    G.inv[2] = (a[1] * a[5] - a[2] * a[4]) / det;
+    G.inv[3] = (a[5] * a[6] - a[3] * a[8]) / det;
+    G.inv[4] = (a[0] * a[8] - a[2] * a[6]) / det;
+    G.inv[5] = (a[2] * a[3] - a[0] * a[5]) / det;
+    G.inv[6] = (a[3] * a[7] - a[4] * a[6]) / det;
+    G.inv[7] = (a[1] * a[6] - a[0] * a[7]) / det;
+    G.inv[8] = (a[0] * a[4] - a[1] * a[3]) / det;
+    for (int k = 0; k < 3; ++k) {  // height along k = |det| / |a_{k+1} x a_{k+2}|
+      const double* u = a + 3 * ((k + 1) % 3);
+      const double* v = a + 3 * ((k + 2) % 3);
+      const double cx = u[1] * v[2] - u[2] * v[1], cy = u[2] * v[0] - u[0] * v[2],
+                   cz = u[0] * v[1] - u[1] * v[0];
+      hgt[k] = std::fabs(det) / std::sqrt(cx * cx + cy * cy + cz * cz);
+    }
+  } else {
+    // isolated cluster: a virtual orthorhombic box 1 A beyond the atoms on
+    // every side, so no image is ever within the cutoff (S = 0 throughout)
+    std::vector<double> hp((size_t)n * 3);
+    if (n) HIPCHK(hipMemcpy(hp.data(), pos, hp.size() * 8, hipMemcpyDefault));
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    for (int64_t a = 0; a < n; ++a)
+      for (int k = 0; k < 3; ++k) {
+        const double v = hp[3 * a + k];
+        if (!std::isfinite(v)) return fail(E3GNN_ERR_ARG, "non-finite position");
+        lo[k] = a ? std::min(lo[k], v) : v;
+        hi[k] = a ? std::max(hi[k], v) : v;
+      }
+    for (int k = 0; k < 3; ++k) {
+      G.origin[k] = lo[k] - 1.0;
+      hgt[k] = (hi[k] - lo[k]) + 2.0;
+      G.cell[4 * k] = hgt[k];
+      G.inv[4 * k] = 1.0 / hgt[k];
+    }
+  }
+  nl_bins(G, hgt, cutoff, n);
+  const int nbins = G.nb[0] * G.nb[1] * G.nb[2];
+  if (h->f0.ensure((size_t)std::max<int64_t>(n, 1) * 12) != hipSuccess ||
+      h->bin.ensure((size_t)std::max<int64_t>(n, 1) * 4) != hipSuccess ||
+      h->bin_atoms.ensure((size_t)std::max<int64_t>(n, 1) * 4) != hipSuccess ||
+      h->deg.ensure((size_t)std::max<int64_t>(n, 1) * 4) != hipSuccess ||
+      h->row_ptr.ensure((size_t)(n + 1) * 4) != hipSuccess ||
+      h->bin_count.ensure((size_t)nbins * 4) != hipSuccess ||
+      h->bin_start.ensure((size_t)(nbins + 1) * 4) != hipSuccess ||
+      h->cursor.ensure((size_t)nbins * 4) != hipSuccess || h->err.ensure(4) != hipSuccess)
+    return fail(E3GNN_ERR_HIP, "neighbour-list workspace allocation failed");
+  int* err = h->err.i();
+  HIPCHK(hipMemsetAsync(err, 0, 4, s));
+  HIPCHK(hipMemsetAsync(h->bin_count.p, 0, (size_t)nbins * 4, s));
+  HIPCHK(hipMemsetAsync(h->cursor.p, 0, (size_t)nbins * 4, s));
+  HIPCHK(launch_nl_bin((int)n, pos, G, h->f0.i(), h->bin.i(), h->bin_count.i(), err, s));
+  HIPCHK(launch_nl_scan(nbins, h->bin_count.i(), h->bin_start.i(), s));
+  HIPCHK(launch_nl_place((int)n, h->bin.i(), h->bin_start.i(), h->cursor.i(), h->bin_atoms.i(), s));
+  return E3GNN_OK;
+}
+}  // namespace
+
+int e3gnn_nlist_build(e3gnn_nlist* h, int64_t n, const double* pos, const double* cell,
+                      const int* pbc, double cutoff, int64_t* n_edges, void* stream) {
+  if (!h) return fail(E3GNN_ERR_ARG, "null neighbour-list handle");
+  if (n < 0 || n >= (int64_t)1 << 30) return fail(E3GNN_ERR_ARG, "atom count out of range");
+  if (!(cutoff > 0)) return fail(E3GNN_ERR_ARG, "cutoff must be positive");
+  if (n > 0 && !pos) return fail(E3GNN_ERR_ARG, "null positions");
+  if (!pbc) return fail(E3GNN_ERR_ARG, "null pbc flags");
+  const bool all = pbc[0] && pbc[1] && pbc[2], none = !pbc[0] && !pbc[1] && !pbc[2];
+  if (!all && !none)
+    return fail(E3GNN_ERR_ARG, "device neighbour list: pbc must be all true or all false");
+  hipStream_t s = (hipStream_t)stream;
+  if (const int rc = nl_bin_atoms(h, n, pos, cell, all, cutoff, s)) return rc;
+  const NlGeom& G = h->G;
+  int* err = h->err.i();
+  HIPCHK(launch_nl_search(false, (int)n, pos, G, h->f0.i(), h->bin.i(), h->bin_start.i(),
+                          h->bin_atoms.i(), h->deg.i(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                          err, s));
+  if (n > 0) HIPCHK(launch_nl_scan((int)n, h->deg.i(), h->row_ptr.i(), s));
+  int herr = 0, total = 0;
+  HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
+  if (n > 0) HIPCHK(hipMemcpyAsync(&total, h->row_ptr.i() + n, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (herr & 1) return fail(E3GNN_ERR_ARG, "non-finite or out-of-box atom position");
+  if (herr & 4)
+    return fail(E3GNN_ERR_GRAPH, "a centre has more than " + std::to_string(NL_MAXD) +
+                                     " neighbours (device neighbour-list limit)");
+  if (total < 0) return fail(E3GNN_ERR_GRAPH, "edge count exceeds int32");
+  h->E = total;
+  h->built = true;
+  if (n_edges) *n_edges = total;
+  return E3GNN_OK;
+}
+
+int e3gnn_nlist_fetch(e3gnn_nlist* h, int32_t* center, int32_t* nbr, int32_t* shift, float* vec,
+                      void* stream) {
+  if (!h || !h->built) return fail(E3GNN_ERR_ARG, "neighbour list not built");
+  if (h->E > 0 && (!center || !nbr)) return fail(E3GNN_ERR_ARG, "null edge output");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  int* err = h->err.i();
+  HIPCHK(hipMemsetAsync(err, 0, 4, s));
+  HIPCHK(launch_nl_search(true, (int)h->n, h->pos, h->G, h->f0.i(), h->bin.i(), h->bin_start.i(),
+                          h->bin_atoms.i(), nullptr, h->row_ptr.i(), center, nbr, shift, vec, err,
+                          s));
+  int herr = 0;
+  HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (herr & 2) return fail(E3GNN_ERR_GRAPH, "periodic image shift beyond +-1024 cells");
+  return E3GNN_OK;
+}
+
+namespace {
+// Argument rules of e3gnn_nlist_rank_build, checked before any device work
+// (host only: no handle state, no HIP call).  Returns the refusal or nullptr.
+const char* nl_rank_args(bool have_handle, int64_t n, const double* pos, const double* cell,
+                         double cutoff, const int32_t* owner, int rank, int world) {
+  if (world < 1 || world > NL_MAX_WORLD) return "rank graph: world must be in [1, 256]";
+  if (rank < 0 || rank >= world) return "rank graph: rank outside [0, world)";
+  if (!have_handle) return "null neighbour-list handle";
+  if (n < 0 || n >= (int64_t)1 << 30) return "atom count out of range";
+  if (!(cutoff > 0)) return "cutoff must be positive";
+  if (n > 0 && !pos) return "null positions";
+  if (n > 0 && !owner) return "rank graph: null owner array";
+  if (!cell) return "rank graph: null cell (all three dimensions must be periodic)";
+  return nullptr;
+}
+}  // namespace
+
+int e3gnn_nlist_rank_build(e3gnn_nlist* h, int64_t n, const double* pos, const double* cell,
+                           double cutoff, const int32_t* owner, int rank, int world,
+                           int64_t* n_local, int64_t* n_interior, int64_t* n_ghost,
+                           int64_t* n_edges, void* stream) {
+  static_assert(NL_MAX_WORLD == 256, "message of nl_rank_args");
+  if (const char* why = nl_rank_args(h != nullptr, n, pos, cell, cutoff, owner, rank, world))
+    return fail(E3GNN_ERR_ARG, why);
+  hipStream_t s = (hipStream_t)stream;
+  if (const int rc = nl_bin_atoms(h, n, pos, cell, true, cutoff, s)) return rc;
+  const NlGeom& G = h->G;
+  int* err = h->err.i();
+  const size_t n1 = (size_t)std::max<int64_t>(n, 1);
+  if (h->flag.ensure(n1 * 4) != hipSuccess || h->fpos.ensure((n1 + 1) * 4) != hipSuccess ||
+      h->lid.ensure(n1 * 4) != hipSuccess || h->recv.ensure((size_t)world * 8) != hipSuccess ||
+      h->sc_sum.ensure((size_t)nl_scan_blocks((int)n) * 4) != hipSuccess ||
+      h->sc_off.ensure(((size_t)nl_scan_blocks((int)n) + 1) * 4) != hipSuccess)
+    return fail(E3GNN_ERR_HIP, "rank-graph workspace allocation failed");
+  // the scans run over many workgroups (per-atom arrays; workspaces sized above and below)
+  auto scan = [&](int m, const int* cnt, int* out) {
+    return launch_rk_scan(m, cnt, out, h->sc_sum.i(), h->sc_off.i(), s);
+  };
+  // the rank's atoms in id order
+  HIPCHK(launch_rk_mark((int)n, owner, rank, world, h->flag.i(), err, s));
+  HIPCHK(scan((int)n, h->flag.i(), h->fpos.i()));
+  int herr = 0, nc = 0;
+  HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&nc, h->fpos.i() + n, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (herr & 1) return fail(E3GNN_ERR_ARG, "non-finite or out-of-box atom position");
+  if (herr & 8) return fail(E3GNN_ERR_GRAPH, "rank graph: an owner value is outside [0, world)");
+  const size_t nc1 = (size_t)std::max(nc, 1);
+  if (h->centers.ensure(nc1 * 4) != hipSuccess || h->bflag.ensure(nc1 * 4) != hipSuccess ||
+      h->degrow.ensure(nc1 * 4) != hipSuccess || h->owned.ensure(nc1 * 4) != hipSuccess ||
+      h->gid.ensure(n1 * 4) != hipSuccess)
+    return fail(E3GNN_ERR_HIP, "rank-graph workspace allocation failed");
+  HIPCHK(launch_rk_compact((int)n, h->flag.i(), h->fpos.i(), h->centers.i(), s));
+  // count pass: degrees, boundary flags, ghost flags (h->flag from here on)
+  HIPCHK(hipMemsetAsync(h->flag.p, 0, n1 * 4, s));
+  HIPCHK(hipMemsetAsync(h->lid.p, 0xff, n1 * 4, s));
+  NlRank rk{};
+  rk.centers = h->centers.i();
+  rk.owner = owner;
+  rk.rank = rank;
+  rk.boundary_flag = h->bflag.i();
+  rk.ghost_flag = h->flag.i();
+  HIPCHK(launch_nl_rank_search(false, nc, pos, G, h->f0.i(), h->bin.i(), h->bin_start.i(),
+                               h->bin_atoms.i(), h->deg.i(), nullptr, nullptr, nullptr, nullptr,
+                               nullptr, err, rk, s));
+  // rows: interior then boundary; degrees in row order -> row_ptr
+  int nbnd = 0, total = 0, ng = 0;
+  HIPCHK(scan(nc, h->bflag.i(), h->fpos.i()));
+  HIPCHK(hipMemcpyAsync(&nbnd, h->fpos.i() + nc, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(launch_rk_rows(nc, h->centers.i(), h->bflag.i(), h->fpos.i(), h->deg.i(), h->owned.i(),
+                        h->degrow.i(), h->lid.i(), s));
+  HIPCHK(scan(nc, h->degrow.i(), h->row_ptr.i()));
+  HIPCHK(hipMemcpyAsync(&total, h->row_ptr.i() + nc, 4, hipMemcpyDeviceToHost, s));
+  // ghosts in id order
+  HIPCHK(scan((int)n, h->flag.i(), h->fpos.i()));
+  HIPCHK(launch_rk_compact((int)n, h->flag.i(), h->fpos.i(), h->gid.i(), s));
+  HIPCHK(hipMemcpyAsync(&ng, h->fpos.i() + n, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (herr & 4)
+    return fail(E3GNN_ERR_GRAPH, "a centre has more than " + std::to_string(NL_MAXD) +
+                                     " neighbours (device neighbour-list limit)");
+  if (total < 0) return fail(E3GNN_ERR_GRAPH, "edge count exceeds int32");
+  // ghosts by (owner, id): stable counting sort over blocks of 256
+  const int nblk = std::max(1, (ng + 255) / 256);
+  const size_t nh = (size_t)world * nblk;
+  if (h->ghosts.ensure((size_t)std::max(ng, 1) * 4) != hipSuccess ||
+      h->hist.ensure(nh * 4) != hipSuccess || h->hoff.ensure((nh + 1) * 4) != hipSuccess ||
+      h->sc_sum.ensure((size_t)nl_scan_blocks((int)nh) * 4) != hipSuccess ||
+      h->sc_off.ensure(((size_t)nl_scan_blocks((int)nh) + 1) * 4) != hipSuccess)
+    return fail(E3GNN_ERR_HIP, "rank-graph workspace allocation failed");
+  HIPCHK(launch_rk_ghost_sort(false, ng, world, nblk, h->gid.i(), owner, h->hist.i(), nullptr, nc,
+                              nullptr, nullptr, s));
+  HIPCHK(scan((int)nh, h->hist.i(), h->hoff.i()));
+  HIPCHK(launch_rk_ghost_sort(true, ng, world, nblk, h->gid.i(), owner, nullptr, h->hoff.i(), nc,
+                              h->ghosts.i(), h->lid.i(), s));
+  HIPCHK(launch_rk_recv(world, nblk, h->hoff.i(), (int64_t*)h->recv.p, s));
+  HIPCHK(hipStreamSynchronize(s));
+  h->n_local = nc;
+  h->n_ghost = ng;
+  h->world = world;
+  h->E = total;
+  h->rank_built = true;
+  if (n_local) *n_local = nc;
+  if (n_interior) *n_interior = nc - nbnd;
+  if (n_ghost) *n_ghost = ng;
+  if (n_edges) *n_edges = total;
+  return E3GNN_OK;
+}
+
+int e3gnn_nlist_rank_fetch(e3gnn_nlist* h, int32_t* owned, int32_t* ghosts, int64_t* recv_counts,
+                           int32_t* edge_center, int32_t* edge_nbr, int32_t* shift,
+                           float* edge_vec, void* stream) {
+  if (!h || !h->rank_built) return fail(E3GNN_ERR_ARG, "rank graph not built");
+  if ((h->n_local > 0 && !owned) || (h->n_ghost > 0 && !ghosts) || !recv_counts ||
+      (h->E > 0 && (!edge_center || !edge_nbr)))
+    return fail(E3GNN_ERR_ARG, "null rank-graph output");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  int* err = h->err.i();
+  HIPCHK(hipMemsetAsync(err, 0, 4, s));
+  if (h->n_local)
+    HIPCHK(hipMemcpyAsync(owned, h->owned.p, (size_t)h->n_local * 4, hipMemcpyDeviceToDevice, s));
+  if (h->n_ghost)
+    HIPCHK(hipMemcpyAsync(ghosts, h->ghosts.p, (size_t)h->n_ghost * 4, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(recv_counts, h->recv.p, (size_t)h->world * 8, hipMemcpyDeviceToDevice, s));
+  // fill pass: one wave per local row (the centres in row order)
+  NlRank rk{};
+  rk.centers = h->owned.i();
+  rk.lid = h->lid.i();
+  HIPCHK(launch_nl_rank_search(true, (int)h->n_local, h->pos, h->G, h->f0.i(), h->bin.i(),
+                               h->bin_start.i(), h->bin_atoms.i(), nullptr, h->row_ptr.i(),
+                               edge_center, edge_nbr, shift, edge_vec, err, rk, s));
+  int herr = 0;
+  HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (herr & 2) return fail(E3GNN_ERR_GRAPH, "periodic image shift beyond +-1024 cells");
+  return E3GNN_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // e3nn o3.Linear(biases=True) (use_bias_in_linear), shared by the host sides of
-// both engines (api.cpp, generic.cpp): the bias over the full output row -- b
+// both engines (model_load.cpp, generic.cpp): the bias over the full output row -- b
 // on the channels of every scalar (0e) output irrep, in output order, zero
 // elsewhere.  `scalar(irrep)` says which irreps carry a bias; `name` is the
 // tensor, for the error of a bias of the wrong size.

@@ -1,5 +1,5 @@
 // Grow-only device buffer and host -> device upload, shared by the host
-// translation units of libe3gnn_hip.so (api.cpp, generic.cpp).
+// translation units of libe3gnn_hip.so (api.cpp, model_load.cpp, generic.cpp and the other api_*.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 

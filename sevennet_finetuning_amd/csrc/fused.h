@@ -7,19 +7,14 @@ namespace e3gnn {
 
 struct MlpW {
   const float* w0;   // [8][64]   layer0 / sqrt(8)
-  const float* w1;   // [64][64]  layer1 / 8
-  const float* w2;   // [64][W]   layer2 / 8
-  const float* w2t;  // [W][64]   transpose of w2
-  // packed operand orders (16 k-values of one lane group contiguous):
-  const float* w1p;  // [n<64][g][q][t] = w1[16q + 4g + t][n]
-  const float* w2p;  // [n<W][g][q][t]  = w2[16q + 4g + t][n]
-  const float* w2q;  // [n/16][bh][g][c][s] = w2[16bh + c][16(n/16) + 4s + g]
-  const float* w2r;  // [n/16][bh][g][c][r] = w2[16bh + c][16(n/16) + 4g + r] (fused bwd)
+  // w2 = layer2 / 8 ([64][W]) in the f32 operand order of the last block's
+  // backward in its six-product reference form (E3GNN_DH2_X3=0):
+  const float* w2r;  // [n/16][bh][g][c][r] = w2[16bh + c][16(n/16) + 4g + r]
   // w2 as three bf16 pieces (w2 = p0 + p1 + p2, exact) in v_mfma_f32_16x16x32_bf16
   // operand order: [n/16][piece][m][g][c][t] = piece of w2[16(2m + t/4) + 4g + t%4][n]
   const uint16_t* w2b;
   // the last block's dH2 operand over PAIRS of consecutive visited 16-column
-  // blocks (api.cpp bwd_w_block_cols): [pair][piece][bh][g][c][t] = piece of
+  // blocks (model_load.cpp bwd_w_block_cols): [pair][piece][bh][g][c][t] = piece of
   // w2[16 bh + c][col], col = channel 4g + t of the pair's first block (t < 4)
   // or 4g + t - 4 of its second (last block only; null elsewhere)
   const uint16_t* w2d;

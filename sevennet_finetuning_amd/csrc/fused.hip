@@ -123,14 +123,13 @@ __device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
 // does not hoist hundreds of 64-bit addresses out of the centre loop (which it
 // did, and spilled).  Offsets outside the descriptor read 0 (padded rows).
 struct WRes {
-  __amdgpu_buffer_rsrc_t w0, w2p, w2q, w2b, w2r, w2d, w2v, w1b, w1tb, w0tb;
+  __amdgpu_buffer_rsrc_t w0, w2b, w2r, w2d, w2v, w1b, w1tb, w0tb;
 };
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const float* p, int nfloats) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, nfloats * 4, 0x00020000);
 }
 __device__ __forceinline__ WRes make_wres(const MlpW& W, int width) {
-  return {rsrc(W.w0, 8 * 64), rsrc(W.w2p, 64 * width), rsrc(W.w2q, 64 * width),
-          rsrc((const float*)W.w2b, 64 * width * 3 / 2), rsrc(W.w2r, 64 * width),
+  return {rsrc(W.w0, 8 * 64), rsrc((const float*)W.w2b, 64 * width * 3 / 2), rsrc(W.w2r, 64 * width),
           rsrc((const float*)W.w2d, 64 * width * 3 / 2),
           rsrc((const float*)W.w2v, 64 * width * 3 / 2), rsrc((const float*)W.w1b, 64 * 64 * 3 / 2),
           rsrc((const float*)W.w1tb, 64 * 64 * 3 / 2), rsrc((const float*)W.w0tb, 64 * 16 * 3 / 2)};
@@ -613,11 +612,11 @@ __device__ __forceinline__ int next_block_col(int jj) {
     return fn >= 0 ? L::P[fn].woff : -1;
   }
 }
-// w2q blocks of column block col0 (bwd_w dH2 operand): 4 x b128
-__device__ __forceinline__ void load_w2q(f32x4 (&b)[4], __amdgpu_buffer_rsrc_t w2q, int lane, int col0) {
+// w2r blocks of column block col0 (the last block's f32 dH2 operand, E3GNN_DH2_X3=0): 4 x b128
+__device__ __forceinline__ void load_w2r(f32x4 (&b)[4], __amdgpu_buffer_rsrc_t w2r, int lane, int col0) {
   const int v = ((lane >> 4) * 16 + (lane & 15)) * 16;
 #pragma unroll
-  for (int bh = 0; bh < 4; ++bh) b[bh] = ldw4(w2q, v, (col0 / 16 * 4 + bh) * 1024);
+  for (int bh = 0; bh < 4; ++bh) b[bh] = ldw4(w2r, v, (col0 / 16 * 4 + bh) * 1024);
 }
 
 // channel groups (input irrep I, 16-channel block j) in visiting order
@@ -1131,7 +1130,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
               load_gm<L, pi>(gm[0], Rg, vg[0], g, jj);
               load_gm<L, pi>(gm[1], Rg, vg[1], g, jj);
               f32x4 bq[4];   // W2 blocks of the f32 dH2 form
-              if constexpr (!NBR_DH2_BF16) load_w2q(bq, R.w2r, lane, p.woff + 16 * jj);
+              if constexpr (!NBR_DH2_BF16) load_w2r(bq, R.w2r, lane, p.woff + 16 * jj);
               f32x4 wv[2] = {wcur[0], wcur[1]};
               if (nb + 1 < NBLK) {
                 wnxt[0] = w2_block_bwd<false>(hq[0], wq);

@@ -40,8 +40,6 @@
 
 namespace e3gnn {
 
-const GtpTables* gtp_tables(const e3gnn_gtp* g);  // api.cpp
-
 namespace {
 
 struct GIrr {

@@ -1,8 +1,9 @@
 // The generic nequip-family engine behind the C ABI (generic.cpp + generic.hip):
 // every deployment of the reference's E3_equivariant_model that is not
 // SevenNet-0's architecture (pair_e3gnn.cpp:294-386 loads any deployed model;
-// model_build.py:186-445 builds them).  api.cpp routes e3gnn_load, the serial
-// evaluation and the segment API here when the manifest is not SevenNet-0's.
+// model_build.py:186-445 builds them).  model_load.cpp routes e3gnn_load, and
+// api.cpp the serial evaluation and the segment API, here when the manifest is
+// not SevenNet-0's.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+struct e3gnn_gtp;  // the C ABI's path-table handle (include/e3gnn.h)
+
 namespace e3gnn {
 
 // one coupling term: msg[m] += c * h[x] * Y[y] * w[w]
@@ -33,5 +35,8 @@ hipError_t launch_gtp_fwd(int n_centers, const int* row_ptr, const int* nbr, con
 hipError_t launch_gtp_bwd(int n_centers, const int* row_ptr, const int* nbr, const float* h,
                           const float* Y, const float* w, const float* gagg, const GtpTables& T,
                           float* dw, float* dxc, float* dY, hipStream_t s);
+
+// the device tables of a handle made by e3gnn_gtp_create (api_train.cpp)
+const GtpTables* gtp_tables(const e3gnn_gtp* g);
 
 }  // namespace e3gnn

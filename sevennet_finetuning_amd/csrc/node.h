@@ -50,7 +50,7 @@ hipError_t launch_readout(int n, int D, const float* x, const float* v, const in
 hipError_t launch_readout_bwd(int n, int D, const float* v, const int* type, const float* scale,
                               float* dx, hipStream_t s);
 // y[n, d] += b[d] on every row: the linear biases (use_bias_in_linear) after
-// the k_gemm fallback of the node linears (api.cpp); no launch for n == 0
+// the k_gemm fallback of the node linears (api.cpp e3gnn_layer_forward_part); no launch for n == 0
 hipError_t launch_row_bias(int64_t n, int d, const float* b, float* y, hipStream_t s);
 // The FCN readout (readout_as_fcn, FCN_e3nn nn/linear.py:94-129) of the fused
 // engine: a_0 = x, a_k = c f(a_{k-1} M_{k-1}) for the nh hidden layers, s =

@@ -4,7 +4,7 @@
 // (x irrep i, filter irrep l2 in 0e+1e+2e, l3 in |l1-l2|..l1+l2 with l3 <= lmax)
 // one uvu instruction; weight slices in instruction order (woff); messages in
 // the stable-sorted-by-l3 mid irreps (moff), convolution.py:82-87.
-// These tables are re-derived from the irreps at model load (api.cpp,
+// These tables are re-derived from the irreps at model load (model_load.cpp,
 // check_path_tables) and the load fails if they ever disagree.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -429,8 +429,10 @@ class LocalHalo(Halo):
     --rank-emulation: one rank of a decomposition timed on one GPU): the
     packs and unpacks of the real Halo run unchanged on the rank's own rows,
     and each all_to_all is replaced by a device copy of the receive buffer's
-    size from the send buffer (rows the rank does not have are left as they
-    were).  The ghost VALUES are therefore not the peers': a timing rehearsal
+    size from the send buffer (rows the rank does not have are zero, never
+    the uninitialised memory of the receive buffer: that could hold NaNs, and
+    the evaluation reads every row).  The ghost VALUES are therefore not the
+    peers': a timing rehearsal
     of one rank's compute and halo kernels, not a physics result."""
 
     staged = False
@@ -443,6 +445,8 @@ class LocalHalo(Halo):
         n = min(out.shape[0], inp.shape[0])
         if n:
             out[:n].copy_(inp[:n])
+        if out.shape[0] > n:
+            out[n:].zero_()
         return [None, None, out]
 
     def forward_start(self, kind, t):

@@ -69,6 +69,15 @@ def test_abi_version_and_errors():
     assert b'coupling' in lib.e3gnn_last_error()
     assert lib.e3gnn_layer_forward(None, 0, None) != 0
     assert lib.e3gnn_ctx_create(None) is None
+    # one refused call per translation unit behind the ABI (csrc/api_train.cpp,
+    # api_nlist.cpp, api_d3.cpp): each sets the library's one last-error string
+    ERR_ARG = 1
+    assert lib.e3gnn_conv_dims(7, None, None, None) == ERR_ARG
+    assert b'conv kind' in lib.e3gnn_last_error()
+    assert lib.e3gnn_nlist_build(None, 0, None, None, None, 5.0, None, None) == ERR_ARG
+    assert b'null neighbour-list handle' in lib.e3gnn_last_error()
+    assert lib.e3gnn_d3_compute(None, 0, None, None, None, None, None, None, None, None) == ERR_ARG
+    assert b'null d3 handle' in lib.e3gnn_last_error()
 
 
 def test_library_is_gfx950_code_object(tmp_path):

@@ -32,7 +32,7 @@ def test_sevennet0_with_options_keeps_the_sevennet0_kernels(opts):
 
 @pytest.mark.parametrize('hidden', [[160], [8, 8, 8, 8, 8], []])
 def test_fcn_beyond_the_readout_kernel_limits_is_not_sevennet0(hidden):
-    """What e3gnn_load sends to the generic engine (fused_family, csrc/api.cpp)."""
+    """What e3gnn_load sends to the generic engine (fused_family, csrc/model_load.cpp)."""
     man = _sevennet0_manifest(readout_as_fcn=True)
     man['readout'] = dict(man['readout'], hidden=hidden)
     assert sevennet0_kinds(man) is None

@@ -8,8 +8,10 @@
 // of column order; the image is packed by the header's packer and staged in
 // LDS as k_conv_bwd_ls stages it (256 threads, tid-strided b128 copy).
 //   w2_dual_image              the whole test (needs a gfx950 device)
-//   w2_dual_image --host-only  packer against the index formulas only: the
-//                              reads are emulated on the host (no device)
+//   w2_dual_image --host-only  packers against the index formulas only: the
+//                              reads are emulated on the host, and the w2b /
+//                              w2v / w2d packers of csrc/mlp_images.h must
+//                              equal the restated formulas (no device)
 // Build: hipcc --offload-arch=gfx950 -O2 -std=c++17 w2_dual_image.hip -o w2_dual_image
 // (the host part also under -Xarch_host -fsanitize=address,undefined, run --host-only)
 #include <hip/hip_runtime.h>
@@ -17,9 +19,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include "../../sevennet_finetuning_amd/csrc/mlp_images.h"
 #include "../../sevennet_finetuning_amd/csrc/w2_image.h"
 
 namespace wi = e3gnn::w2img;
+namespace mi = e3gnn::mlpimg;
 constexpr int W = 64, NPAIR = 2, NWAVE = 4;
 static const int COLS[2 * NPAIR] = {16, 48, 32, 0};   // visiting order of the 16-column blocks
 
@@ -101,7 +105,9 @@ int main(int argc, char** argv) {
   std::vector<uint16_t> s2((size_t)NPAIR * wi::PAIR_BYTES / 2, 0xdead);
   wi::pack(a2.data(), W, COLS, NPAIR, s2.data());
 
-  // api.cpp's index formulas, restated: the pieces are the bf16 residual chain
+  // the index formulas of mlp_images.h's packers, restated (model_load.cpp
+  // builds the library's images with those packers): the pieces are the bf16
+  // residual chain
   auto piece = [&](int h, int col, int pc) {
     float v = a2[(size_t)h * W + col];
     uint16_t hb = 0;
@@ -174,7 +180,31 @@ int main(int argc, char** argv) {
   }
   printf("host: transposed-read mismatches %d, row-read mismatches %d, off() collisions %d\n", bad_tr, bad_row,
          bad_cover);
-  int bad = bad_tr + bad_row + bad_cover;
+  // the library's packers (mlp_images.h) against the restated formulas, bit
+  // for bit: w2v and w2d above, and w2b = block cb at column 16 cb (w2v's
+  // formula in column order)
+  int bad_pack = 0;
+  {
+    const std::vector<int> cols(COLS, COLS + 2 * NPAIR);
+    auto differs = [](const std::vector<float>& img, const std::vector<uint16_t>& ref) {
+      return img.size() * 4 != ref.size() * 2 || memcmp(img.data(), ref.data(), ref.size() * 2) != 0;
+    };
+    const std::vector<float> b2 = mi::pack_w2b(a2, W);
+    std::vector<uint16_t> b2ref(v2.size());
+    for (int cb = 0; cb < W / 16; ++cb)
+      for (int pc = 0; pc < 3; ++pc)
+        for (int m = 0; m < 2; ++m)
+          for (int g = 0; g < 4; ++g)
+            for (int c = 0; c < 16; ++c)
+              for (int t = 0; t < 8; ++t)
+                b2ref[((((size_t)cb * 3 + pc) * 2 + m) * 64 + g * 16 + c) * 8 + t] =
+                    piece(16 * (2 * m + t / 4) + 4 * g + t % 4, 16 * cb + c, pc);
+    bad_pack += differs(b2, b2ref);
+    bad_pack += differs(mi::pack_w2v(b2, cols), v2);
+    bad_pack += differs(mi::pack_w2d(a2, W, cols), d2);
+  }
+  printf("host: packer images (w2b, w2v, w2d) differing from the formulas %d\n", bad_pack);
+  int bad = bad_tr + bad_row + bad_cover + bad_pack;
   if (host_only) return bad != 0;
 
   std::vector<uint16_t> hq((size_t)NWAVE * 2 * 2 * 64 * 8), dq((size_t)NWAVE * 2 * 64 * 8);
