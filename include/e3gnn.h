@@ -216,6 +216,15 @@ float* e3gnn_grad_ptr(e3gnn_ctx* c, int layer);
 /* Forces on all n_local+n_ghost rows (ghost rows: reverse-communicate),
  * rank-local virial6 and optional edge_grad[E*3]. */
 int e3gnn_forces(e3gnn_ctx* c, float* forces, float* virial6, float* edge_grad, void* stream);
+/* Per-atom virial of the last e3gnn_forces / e3gnn_energy_forces on this
+ * context: atom_virial6[(n_local+n_ghost)*6], (xx,yy,zz,xy,yz,zx) per row, the
+ * edge-gradient partition -- every edge's virial term -voigt(edge_vec, dE/dedge_vec)
+ * in halves to its centre and its neighbour, so the rows sum to virial6.  Ghost
+ * rows hold their neighbour-side halves: reverse-communicate them like the
+ * ghost forces.  Enqueued on `stream` (fp32, fixed summation order: bitwise
+ * reproducible).  E3GNN_ERR_ARG before e3gnn_forces or after a new
+ * e3gnn_graph_set.  Not a centroid stress: no heat flux follows from it. */
+int e3gnn_atom_virial(e3gnn_ctx* c, float* atom_virial6, void* stream);
 
 /* ---- halo overlap (the forward_comm / reverse_comm loop of
  * pair_e3gnn_parallel.cpp:371-454, overlapped instead of serialised) ----

@@ -18,9 +18,14 @@
 //       communication.
 // Prints one JSON line: energies, largest force / virial differences, the comm
 // counters (extra rows, relays, zero returns, trash rows) and whether a second
-// compute() reproduced the first bit for bit.
+// compute() reproduced the first bit for bit.  With --vatom both styles also
+// run with VIRIAL_ATOM set, the scaffold reverse-communicates Pair::vatom as
+// compute stress/atom does, and each style's object gains vatom_max_diff
+// (against the library's e3gnn_atom_virial on the whole box, matched by tag),
+// vatom_sum_max_diff (sum over atoms against the style's global virial),
+// vatom_max_ends (most edge ends on one atom) and vatom_repeat_bitwise.
 //
-//   e3gnn_pair_check <model dir> <structure> <px> <py> <pz> [seed] [--gpu-aware]
+//   e3gnn_pair_check <model dir> <structure> <px> <py> <pz> [seed] [--gpu-aware] [--vatom]
 //   structure: si:<cells> (displaced Si diamond) or a file
 //              "n \n 9 cell values (rows = lattice vectors) \n symbol x y z ..."
 #include <hip/hip_runtime.h>
@@ -116,16 +121,17 @@ Structure load_structure(const std::string& spec, std::mt19937& rng) {
 struct RankOut {
   double energy = 0, virial[6] = {0, 0, 0, 0, 0, 0}, eatom = 0;
   std::vector<std::pair<tagint, std::array<double, 3>>> f;   // owned atoms
+  std::vector<std::pair<tagint, std::array<double, 6>>> vatom;   // owned atoms (--vatom)
   e3gnn_pair::CommMaps::Stats st;
   int nghost = 0, graph = 0;
-  bool same_again = true;
+  bool same_again = true, vatom_same_again = true;
   std::string err;
 };
 
 // one emulated MPI rank: LAMMPS-style setup, pair_style / pair_coeff, then
 // `repeat` force evaluations (each: borders, neighbour list, compute, reverse comm)
 void run_rank(const Structure& S, const std::string& model_dir, const int grid[3], int me, World* world,
-              bool parallel, int repeat, std::mutex* load_mutex, RankOut* out) {
+              bool parallel, int repeat, bool want_vatom, std::mutex* load_mutex, RankOut* out) {
   LAMMPS lmp;
   Memory mem;
   Error err;
@@ -183,14 +189,21 @@ void run_rank(const Structure& S, const std::string& model_dir, const int grid[3
   comm.setup(cut + SKIN);
   NeighList list;
   std::vector<std::vector<double>> first;
+  std::vector<double> first_vatom;
   for (int it = 0; it < repeat; ++it) {
     comm.borders();
     neigh.build_full(&atom, cut, &list);
     pair->init_list(0, &list);
     std::fill(atom.fs.begin(), atom.fs.end(), 0.0);
-    pair->compute(1 | 2, 1);
+    pair->compute(1 | 2, want_vatom ? 1 | 4 : 1);   // VIRIAL_PAIR (| VIRIAL_ATOM)
     comm.reverse_comm();   // ghost forces onto their owners (newton on)
     std::vector<double> f(atom.fs.begin(), atom.fs.begin() + 3 * (size_t)atom.nlocal);
+    std::vector<double> va;
+    if (want_vatom) {
+      // what compute stress/atom does before it reads vatom (newton on)
+      comm.reverse_comm_peratom(pair->vatom, 6);
+      for (int i = 0; i < atom.nlocal; ++i) va.insert(va.end(), pair->vatom[i], pair->vatom[i] + 6);
+    }
     if (it == 0) {
       out->energy = pair->eng_vdwl;
       for (int k = 0; k < 6; ++k) out->virial[k] = pair->virial[k];
@@ -198,6 +211,12 @@ void run_rank(const Structure& S, const std::string& model_dir, const int grid[3
         out->eatom += pair->eatom[i];
         out->f.push_back({atom.tag[i], {f[3 * i], f[3 * i + 1], f[3 * i + 2]}});
       }
+      for (int i = 0; want_vatom && i < atom.nlocal; ++i) {
+        std::array<double, 6> w;
+        std::copy(va.begin() + 6 * (size_t)i, va.begin() + 6 * (size_t)i + 6, w.begin());
+        out->vatom.push_back({atom.tag[i], w});
+      }
+      first_vatom = va;
       out->nghost = atom.nghost;
       if (parallel) {
         auto* pp = static_cast<PairE3GNNParallel*>(pair.get());
@@ -206,6 +225,7 @@ void run_rank(const Structure& S, const std::string& model_dir, const int grid[3
       first.push_back(f);
     } else {
       out->same_again = out->same_again && f == first[0] && pair->eng_vdwl == out->energy;
+      out->vatom_same_again = out->vatom_same_again && va == first_vatom;
     }
   }
 }
@@ -213,12 +233,14 @@ void run_rank(const Structure& S, const std::string& model_dir, const int grid[3
 struct RunOut {
   double energy = 0, virial[6] = {0, 0, 0, 0, 0, 0}, eatom = 0;
   std::vector<double> f_tag;   // by tag - 1
+  std::vector<double> vatom_tag;   // by tag - 1, LAMMPS order (--vatom)
   e3gnn_pair::CommMaps::Stats st;
   int64_t ghosts = 0;
-  bool same_again = true;
+  bool same_again = true, vatom_same_again = true;
 };
 
-RunOut run(const Structure& S, const std::string& dir, const int grid[3], bool parallel, int repeat) {
+RunOut run(const Structure& S, const std::string& dir, const int grid[3], bool parallel, int repeat,
+           bool want_vatom) {
   const int P = grid[0] * grid[1] * grid[2];
   World world(P);
   std::mutex load_mutex;
@@ -228,7 +250,7 @@ RunOut run(const Structure& S, const std::string& dir, const int grid[3], bool p
     th.emplace_back([&, r] {
       try {
         if (hipSetDevice(0) != hipSuccess) throw std::runtime_error("hipSetDevice");
-        run_rank(S, dir, grid, r, &world, parallel, repeat, &load_mutex, &outs[r]);
+        run_rank(S, dir, grid, r, &world, parallel, repeat, want_vatom, &load_mutex, &outs[r]);
       } catch (const std::exception& e) {
         outs[r].err = e.what();
         world.abort();
@@ -240,6 +262,7 @@ RunOut run(const Structure& S, const std::string& dir, const int grid[3], bool p
       throw std::runtime_error("rank " + std::to_string(r) + ": " + outs[r].err);
   RunOut R;
   R.f_tag.assign(3 * (size_t)S.n, 0.0);
+  if (want_vatom) R.vatom_tag.assign(6 * (size_t)S.n, 0.0);
   std::vector<int> seen(S.n, 0);
   for (auto& o : outs) {
     R.energy += o.energy;
@@ -249,8 +272,11 @@ RunOut run(const Structure& S, const std::string& dir, const int grid[3], bool p
       seen[t - 1]++;
       for (int k = 0; k < 3; ++k) R.f_tag[3 * (t - 1) + k] = f[k];
     }
+    for (auto& [t, w] : o.vatom)
+      for (int k = 0; k < 6; ++k) R.vatom_tag[6 * (t - 1) + k] = w[k];
     R.ghosts += o.nghost;
     R.same_again = R.same_again && o.same_again;
+    R.vatom_same_again = R.vatom_same_again && o.vatom_same_again;
     R.st.swaps += o.st.swaps;
     R.st.sent += o.st.sent;
     R.st.relayed += o.st.relayed;
@@ -268,14 +294,16 @@ RunOut run(const Structure& S, const std::string& dir, const int grid[3], bool p
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s model_dir structure px py pz [seed] [--gpu-aware]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s model_dir structure px py pz [seed] [--gpu-aware] [--vatom]\n", argv[0]);
     return 2;
   }
   const std::string dir = argv[1];
   const int grid[3] = {std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5])};
   unsigned seed = 0;
+  bool want_vatom = false;
   for (int k = 6; k < argc; ++k) {
     if (!std::strcmp(argv[k], "--gpu-aware")) setenv("E3GNN_GPU_AWARE_MPI", "1", 1);
+    else if (!std::strcmp(argv[k], "--vatom")) want_vatom = true;
     else seed = (unsigned)std::atoi(argv[k]);
   }
   try {
@@ -294,6 +322,8 @@ int main(int argc, char** argv) {
       ty[S.tag[a] - 1] = map[S.type[a]];
     }
     double e_ref = 0, v_ref[6];
+    std::vector<double> w_ref;   // --vatom: e3gnn_atom_virial by tag - 1, LAMMPS order
+    int max_ends = 0;            // ... and the most edge ends (centre + neighbour side) on one atom
     {
       e3gnn_ctx* ctx = e3gnn_ctx_create(model.handle());
       e3gnn_nlist* nl = e3gnn_nlist_create(0);
@@ -324,6 +354,27 @@ int main(int argc, char** argv) {
       const float* v6 = sc + 1;   // (xx, yy, zz, xy, yz, zx) -> LAMMPS (xx, yy, zz, xy, xz, yz)
       const double vl[6] = {v6[0], v6[1], v6[2], v6[3], v6[5], v6[4]};
       for (int k = 0; k < 6; ++k) v_ref[k] = vl[k];
+      if (want_vatom) {
+        float* dw;
+        (void)hipMalloc(&dw, (size_t)n * 24);
+        if (e3gnn_atom_virial(ctx, dw, nullptr)) throw std::runtime_error(e3gnn_last_error());
+        std::vector<float> hw(6 * (size_t)n);
+        std::vector<int32_t> hc(E), hn(E);
+        (void)hipMemcpy(hw.data(), dw, (size_t)n * 24, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(hc.data(), dc, E * 4, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(hn.data(), dn, E * 4, hipMemcpyDeviceToHost);
+        (void)hipFree(dw);
+        const int lmp_of[6] = {0, 1, 2, 3, 5, 4};
+        w_ref.resize(6 * (size_t)n);
+        for (int a = 0; a < n; ++a)
+          for (int k = 0; k < 6; ++k) w_ref[6 * (size_t)a + k] = hw[6 * (size_t)a + lmp_of[k]];
+        std::vector<int> ends(n, 0);
+        for (int64_t e = 0; e < E; ++e) {
+          ends[hc[e]]++;
+          ends[hn[e]]++;
+        }
+        max_ends = n ? *std::max_element(ends.begin(), ends.end()) : 0;
+      }
       for (void* p : {(void*)dp, (void*)dc, (void*)dn, (void*)dv, (void*)dt, (void*)df, (void*)ds})
         (void)hipFree(p);
       e3gnn_nlist_free(nl);
@@ -341,25 +392,41 @@ int main(int argc, char** argv) {
     };
 
     const int one[3] = {1, 1, 1};
-    const RunOut ser = run(S, dir, one, false, 2);
-    const RunOut par = run(S, dir, grid, true, 2);
+    const RunOut ser = run(S, dir, one, false, 2, want_vatom);
+    const RunOut par = run(S, dir, grid, true, 2, want_vatom);
     const double scale = std::fabs(e_ref);
+    // --vatom: the extra keys of a style's object (empty without the flag)
+    auto vatom_keys = [&](const RunOut& R) -> std::string {
+      if (!want_vatom) return "";
+      double sum[6] = {0, 0, 0, 0, 0, 0};
+      for (int a = 0; a < n; ++a)
+        for (int k = 0; k < 6; ++k) sum[k] += R.vatom_tag[6 * (size_t)a + k];
+      char buf[256];
+      std::snprintf(buf, sizeof(buf),
+                    ", \"vatom_max_diff\": %.3e, \"vatom_sum_max_diff\": %.3e, \"vatom_max_ends\": %d, "
+                    "\"vatom_repeat_bitwise\": %s",
+                    max_diff(R.vatom_tag, w_ref), max_vdiff(sum, R.virial), max_ends,
+                    R.vatom_same_again ? "true" : "false");
+      return buf;
+    };
+    const std::string vs = vatom_keys(ser), vp = vatom_keys(par);
     std::printf(
         "{\"n_atoms\": %d, \"ranks\": %d, \"energy_ref\": %.8f, \"max_virial_ref\": %.6e, "
         "\"serial\": {\"energy\": %.8f, \"energy_rel\": %.3e, \"max_force\": %.3e, \"max_virial\": %.3e, "
-        "\"eatom_sum_rel\": %.3e, \"repeat_bitwise\": %s}, "
+        "\"eatom_sum_rel\": %.3e, \"repeat_bitwise\": %s%s}, "
         "\"parallel\": {\"energy\": %.8f, \"energy_rel\": %.3e, \"max_force\": %.3e, \"max_virial\": %.3e, "
         "\"eatom_sum_rel\": %.3e, \"repeat_bitwise\": %s, \"vs_serial_energy_rel\": %.3e, "
-        "\"vs_serial_max_force\": %.3e}, "
+        "\"vs_serial_max_force\": %.3e%s}, "
         "\"comm\": {\"ghosts\": %lld, \"swaps\": %lld, \"sent\": %lld, \"relayed\": %lld, \"extra_rows\": %lld, "
         "\"zero_sends\": %lld, \"trash_forward\": %lld, \"trash_reverse\": %lld}}\n",
         n, grid[0] * grid[1] * grid[2], e_ref, std::max(std::fabs(*std::max_element(v_ref, v_ref + 6)),
                                                        std::fabs(*std::min_element(v_ref, v_ref + 6))),
         ser.energy, std::fabs(ser.energy - e_ref) / scale, max_diff(ser.f_tag, f_ref), max_vdiff(ser.virial, v_ref),
-        std::fabs(ser.eatom - e_ref) / scale, ser.same_again ? "true" : "false", par.energy,
+        std::fabs(ser.eatom - e_ref) / scale, ser.same_again ? "true" : "false", vs.c_str(), par.energy,
         std::fabs(par.energy - e_ref) / scale, max_diff(par.f_tag, f_ref), max_vdiff(par.virial, v_ref),
         std::fabs(par.eatom - e_ref) / scale, par.same_again ? "true" : "false",
-        std::fabs(par.energy - ser.energy) / scale, max_diff(par.f_tag, ser.f_tag), (long long)par.ghosts,
+        std::fabs(par.energy - ser.energy) / scale, max_diff(par.f_tag, ser.f_tag), vp.c_str(),
+        (long long)par.ghosts,
         (long long)par.st.swaps, (long long)par.st.sent, (long long)par.st.relayed, (long long)par.st.extra_rows,
         (long long)par.st.zero_sends, (long long)par.st.trash_forward, (long long)par.st.trash_reverse);
   } catch (const std::exception& e) {

@@ -33,6 +33,9 @@ PairE3GNN::PairE3GNN(LAMMPS *lmp) : Pair(lmp)
   restartinfo = 0;
   one_coeff = 1;
   manybody_flag = 1;
+  // vatom is the edge-gradient partition of the virial (e3gnn_atom_virial);
+  // a message-passing model has no centroid form of it
+  centroidstressflag = CENTROID_NOTAVAIL;
   // the reference picks the GPU by rank (pair_e3gnn_parallel.cpp:153-189);
   // one rank per GPU here too
   device = comm->me;
@@ -49,7 +52,6 @@ PairE3GNN::~PairE3GNN()
 void PairE3GNN::compute(int eflag, int vflag)
 {
   ev_init(eflag, vflag);
-  if (vflag_atom) error->all(FLERR, "atomic stress is not supported");
   if (atom->tag_consecutive() == 0) error->all(FLERR, "Pair e3gnn requires consecutive atom IDs");
 
   const int ntotal = atom->nlocal + atom->nghost;
@@ -69,7 +71,7 @@ void PairE3GNN::compute(int eflag, int vflag)
   nv.neighmask = NEIGHMASK;
 
   e3gnn_pair::PairOut out;
-  if (step->compute(nv, species, atom->f, eflag_atom ? eatom : nullptr, out))
+  if (step->compute(nv, species, atom->f, eflag_atom ? eatom : nullptr, out, vflag_atom ? vatom : nullptr))
     error->all(FLERR, "e3gnn: " + step->error());
   eng_vdwl += out.energy;
   if (vflag) for (int k = 0; k < 6; k++) virial[k] += out.virial[k];

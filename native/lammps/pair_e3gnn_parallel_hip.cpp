@@ -58,6 +58,9 @@ PairE3GNNParallel::PairE3GNNParallel(LAMMPS *lmp) : Pair(lmp)
   restartinfo = 0;
   one_coeff = 1;
   manybody_flag = 1;
+  // vatom is the edge-gradient partition of the virial (e3gnn_atom_virial);
+  // a message-passing model has no centroid form of it
+  centroidstressflag = CENTROID_NOTAVAIL;
   world_rank = comm->me;
   int ngpu = 1;
   if (hipGetDeviceCount(&ngpu) != hipSuccess || ngpu < 1) ngpu = 1;
@@ -84,7 +87,6 @@ bool PairE3GNNParallel::is_comm_preprocess_done() { return comm_preprocess_done;
 void PairE3GNNParallel::compute(int eflag, int vflag)
 {
   ev_init(eflag, vflag);
-  if (vflag_atom) error->all(FLERR, "atomic stress is not supported");
   if (atom->tag_consecutive() == 0) error->all(FLERR, "Pair e3gnn requires consecutive atom IDs");
   CommBrick *brick = dynamic_cast<CommBrick *>(comm);
   if (!brick)
@@ -112,11 +114,12 @@ void PairE3GNNParallel::compute(int eflag, int vflag)
   ex.pair = this;
   ex.brick = brick;
   e3gnn_pair::PairOut out;
-  if (step->compute(ex, atom->f, eflag_atom ? eatom : nullptr, out))
+  if (step->compute(ex, atom->f, eflag_atom ? eatom : nullptr, out, vflag_atom ? vatom : nullptr))
     error->one(FLERR, "e3gnn/parallel: " + step->error());
   eng_vdwl += out.energy;   // rank-local; LAMMPS sums over ranks
   if (vflag) for (int k = 0; k < 6; k++) virial[k] += out.virial[k];
-  // ghost forces go to their owners with LAMMPS' reverse communication (newton on)
+  // ghost forces go to their owners with LAMMPS' reverse communication (newton
+  // on), and so do the ghost rows of vatom (compute stress/atom's reverse_comm)
   comm_preprocess_done = false;
 }
 

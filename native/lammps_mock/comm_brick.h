@@ -53,6 +53,9 @@ class CommBrick : public Comm {
   void reverse_comm(PairE3GNNParallel *pair);
   // Comm::reverse_comm(): ghost forces summed onto their owners (newton on)
   void reverse_comm();
+  // Comm::reverse_comm(Compute *) of a per-atom array of `width` doubles (what
+  // compute stress/atom does with vatom, width 6): ghost rows summed onto owners
+  void reverse_comm_peratom(double **a, int width);
 
   int nswap = 0;
   int maxsend = 0, maxrecv = 0, bufextra = 0;

@@ -120,6 +120,13 @@ void Pair::ev_init(int eflag, int vflag)
     eatom_s.assign((size_t) atom->nlocal + atom->nghost, 0.0);
     eatom = eatom_s.data();
   }
+  if (vflag_atom) {   // zeroed over nlocal + nghost (newton on), as Pair::ev_setup does
+    const size_t nt = (size_t) atom->nlocal + atom->nghost;
+    vatom_s.assign(6 * nt, 0.0);
+    vatom_p.resize(nt);
+    for (size_t i = 0; i < nt; i++) vatom_p[i] = &vatom_s[6 * i];
+    vatom = vatom_p.data();
+  }
 }
 
 // ------------------------------------------------------------------ World
@@ -366,6 +373,27 @@ void CommBrick::reverse_comm()
     }
     for (int k = 0; k < ns; k++)
       for (int d = 0; d < 3; d++) f[sendlist[iswap][k]][d] += in[3 * k + d];
+  }
+}
+
+// Comm::reverse_comm(Compute *) as compute stress/atom uses it (its
+// pack_reverse_comm / unpack_reverse_comm move the six vatom entries of every
+// ghost): the same swaps as the forces, `width` doubles per atom
+void CommBrick::reverse_comm_peratom(double **a, int width)
+{
+  for (int iswap = nswap - 1; iswap >= 0; iswap--) {
+    const int nr = recvnum[iswap], ns = sendnum[iswap];
+    std::vector<double> out((size_t) width * nr), in((size_t) width * ns);
+    for (int k = 0; k < nr; k++)
+      for (int d = 0; d < width; d++) out[(size_t) width * k + d] = a[firstrecv[iswap] + k][d];
+    if (sendproc[iswap] == me) {
+      in = out;
+    } else {
+      world->sendrecv(me, out.data(), out.size() * sizeof(double), recvproc[iswap], sendproc[iswap], in.data(),
+                      in.size() * sizeof(double), false);
+    }
+    for (int k = 0; k < ns; k++)
+      for (int d = 0; d < width; d++) a[sendlist[iswap][k]][d] += in[(size_t) width * k + d];
   }
 }
 

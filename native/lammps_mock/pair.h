@@ -18,6 +18,9 @@ class Pair : protected Pointers {
   double **cutsq = nullptr;
   int comm_forward = 0, comm_reverse = 0;
   int single_enable = 1, restartinfo = 1, one_coeff = 0, manybody_flag = 0;
+  // pair.h: whether compute centroid/stress/atom can use this style
+  enum { CENTROID_SAME = 0, CENTROID_AVAIL = 1, CENTROID_NOTAVAIL = 2 };
+  int centroidstressflag = CENTROID_SAME;
   int eflag_either = 0, eflag_global = 0, eflag_atom = 0;
   int vflag_either = 0, vflag_global = 0, vflag_atom = 0;
   NeighList *list = nullptr;
@@ -31,6 +34,7 @@ class Pair : protected Pointers {
  protected:
   // ENERGY_GLOBAL = 1, ENERGY_ATOM = 2, VIRIAL_PAIR = 1, VIRIAL_ATOM = 4
   void ev_init(int eflag, int vflag);
-  std::vector<double> eatom_s;
+  std::vector<double> eatom_s, vatom_s;
+  std::vector<double *> vatom_p;
 };
 }  // namespace LAMMPS_NS

@@ -65,6 +65,17 @@ void add_virial(double* lmp, const float* v6) {
   lmp[5] += v6[4];
 }
 
+// LAMMPS vatom row (xx, yy, zz, xy, xz, yz) += a row of e3gnn_atom_virial
+// (xx, yy, zz, xy, yz, zx): the same swap
+void add_vatom(double* lmp, const float* w6) {
+  lmp[0] += w6[0];
+  lmp[1] += w6[1];
+  lmp[2] += w6[2];
+  lmp[3] += w6[3];
+  lmp[4] += w6[5];
+  lmp[5] += w6[4];
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ Model
@@ -108,6 +119,7 @@ void DeviceGraph::reserve(int64_t n, int64_t e) {
     realloc(type, cap_n);
     realloc(forces, 3 * cap_n);
     realloc(atomic, cap_n);
+    realloc(vatom, 6 * cap_n);
   }
   if (e > cap_e || !center) {
     cap_e = e + e / 5 + 64;
@@ -120,10 +132,10 @@ void DeviceGraph::reserve(int64_t n, int64_t e) {
 
 void DeviceGraph::release() {
   for (void* p : {(void*)type, (void*)center, (void*)nbr, (void*)vec, (void*)forces, (void*)atomic,
-                  (void*)scalars})
+                  (void*)scalars, (void*)vatom})
     if (p) (void)hipFree(p);
   type = center = nbr = nullptr;
-  vec = forces = atomic = scalars = nullptr;
+  vec = forces = atomic = scalars = vatom = nullptr;
   cap_n = cap_e = 0;
 }
 
@@ -143,7 +155,7 @@ SerialStep::~SerialStep() {
 }
 
 int SerialStep::compute(const NeighborView& nv, const std::vector<int>& map, double** f,
-                        double* eatom, PairOut& out) {
+                        double* eatom, PairOut& out, double** vatom) {
   const int n = nv.inum;
   const double rc2 = model_.cutoff() * model_.cutoff();
   // nodes = tag - 1 (pair_e3gnn.cpp:146-154; "requires consecutive atom IDs")
@@ -207,6 +219,7 @@ int SerialStep::compute(const NeighborView& nv, const std::vector<int>& map, dou
   }
   CORE_ABI(e3gnn_energy_forces(ctx_, n, nedges_, g_.type, g_.center, g_.nbr, g_.vec, g_.scalars,
                                eatom ? g_.atomic : nullptr, g_.forces, g_.scalars + 1, nullptr, s));
+  if (vatom) CORE_ABI(e3gnn_atom_virial(ctx_, g_.vatom, s));
   float sc[7];
   forces_.resize(3 * (size_t)n);
   CORE_HIP(hipMemcpyAsync(sc, g_.scalars, 7 * 4, hipMemcpyDeviceToHost, s));
@@ -214,6 +227,10 @@ int SerialStep::compute(const NeighborView& nv, const std::vector<int>& map, dou
   if (eatom) {
     atomic_.resize(n);
     CORE_HIP(hipMemcpyAsync(atomic_.data(), g_.atomic, n * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (vatom) {
+    vatom_.resize(6 * (size_t)n);
+    CORE_HIP(hipMemcpyAsync(vatom_.data(), g_.vatom, (size_t)n * 24, hipMemcpyDeviceToHost, s));
   }
   CORE_HIP(hipStreamSynchronize(s));
   // forces added to what LAMMPS zeroed (the reference assigns them; adding keeps
@@ -224,6 +241,8 @@ int SerialStep::compute(const NeighborView& nv, const std::vector<int>& map, dou
     fi[1] += forces_[3 * t + 1];
     fi[2] += forces_[3 * t + 2];
     if (eatom) eatom[tag2i_[t]] += atomic_[t];
+    // rows are tags: every image's half is already on the owned atom
+    if (vatom) add_vatom(vatom[tag2i_[t]], &vatom_[6 * (size_t)t]);
   }
   out.energy += sc[0];
   add_virial(out.virial, sc + 1);
@@ -379,7 +398,7 @@ int ParallelStep::unpack(const int32_t* idx, int64_t n, const float* buf, bool a
   return E3GNN_OK;
 }
 
-int ParallelStep::compute(Exchange& ex, double** f, double* eatom, PairOut& out) {
+int ParallelStep::compute(Exchange& ex, double** f, double* eatom, PairOut& out, double** vatom) {
   hipStream_t s = (hipStream_t)stream_;
   const int L = model_.num_layers();
   const int G = graph_size();
@@ -420,6 +439,7 @@ int ParallelStep::compute(Exchange& ex, double** f, double* eatom, PairOut& out)
     }
   }
   CORE_ABI(e3gnn_forces(ctx_, g_.forces, g_.scalars + 1, nullptr, s));
+  if (vatom) CORE_ABI(e3gnn_atom_virial(ctx_, g_.vatom, s));
   float sc[7];
   forces_.resize(3 * (size_t)G);
   CORE_HIP(hipMemcpyAsync(sc, g_.scalars, 7 * 4, hipMemcpyDeviceToHost, s));
@@ -427,6 +447,10 @@ int ParallelStep::compute(Exchange& ex, double** f, double* eatom, PairOut& out)
   if (eatom) {
     atomic_.resize(nlocal_);
     CORE_HIP(hipMemcpyAsync(atomic_.data(), g_.atomic, nlocal_ * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (vatom) {
+    vatom_.resize(6 * (size_t)G);
+    CORE_HIP(hipMemcpyAsync(vatom_.data(), g_.vatom, (size_t)G * 24, hipMemcpyDeviceToHost, s));
   }
   CORE_HIP(hipStreamSynchronize(s));
   // forces on local AND ghost rows (:480-488): LAMMPS' own reverse
@@ -436,6 +460,9 @@ int ParallelStep::compute(Exchange& ex, double** f, double* eatom, PairOut& out)
     fi[0] += forces_[3 * r];
     fi[1] += forces_[3 * r + 1];
     fi[2] += forces_[3 * r + 2];
+    // ghost rows carry the neighbour-side halves of this rank's edges: the
+    // host's reverse communication of vatom folds them onto their owners
+    if (vatom) add_vatom(vatom[row_to_i_[r]], &vatom_[6 * (size_t)r]);
   }
   if (eatom)
     for (int r = 0; r < nlocal_; ++r) eatom[row_to_i_[r]] += atomic_[r];

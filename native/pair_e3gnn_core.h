@@ -68,6 +68,7 @@ class Model {
 struct DeviceGraph {
   int32_t *type = nullptr, *center = nullptr, *nbr = nullptr;
   float *vec = nullptr, *forces = nullptr, *atomic = nullptr, *scalars = nullptr;
+  float* vatom = nullptr;   // [6 * cap_n] rows of e3gnn_atom_virial
   int64_t cap_n = 0, cap_e = 0;
   void reserve(int64_t n, int64_t e);
   void release();
@@ -79,13 +80,16 @@ struct DeviceGraph {
 // the cutoff, edge_vec = x_j - x_i.  Forces and eatom are ADDED to what the
 // host holds in f / eatom (the reference assigns; adding keeps pair_style
 // hybrid/overlay correct), the energy and virial (LAMMPS order) added to `out`.
+// `vatom` (Pair::vatom, nullable): the per-atom virial of the edge-gradient
+// partition (e3gnn_atom_virial) ADDED to the owned atoms' rows in LAMMPS order
+// (xx, yy, zz, xy, xz, yz); rows are tags, so nothing is left on ghosts.
 class SerialStep {
  public:
   explicit SerialStep(const Model& model);
   ~SerialStep();
   // returns 0, or an E3GNN_ERR_* code with the message in error()
   int compute(const NeighborView& nv, const std::vector<int>& map, double** f, double* eatom,
-              PairOut& out);
+              PairOut& out, double** vatom = nullptr);
   const std::string& error() const { return err_; }
   int64_t last_edges() const { return nedges_; }
 
@@ -95,7 +99,7 @@ class SerialStep {
   void* stream_ = nullptr;
   DeviceGraph g_;
   std::vector<int32_t> type_, center_, nbr_;
-  std::vector<float> vec_, forces_, atomic_;
+  std::vector<float> vec_, forces_, atomic_, vatom_;
   std::vector<int> tag2i_;
   int64_t nedges_ = 0;
   std::string err_;
@@ -109,6 +113,8 @@ class SerialStep {
 // local AND ghost rows are added to f (a ghost row's force to the first-seen
 // LAMMPS image of its atom); the host's own newton-on reverse communication
 // then sums the ghost forces onto their owners -- compute() does not.  The
+// per-atom virial (`vatom`, nullable; LAMMPS order) is added to local and ghost
+// rows in the same way and needs the same reverse communication.  The
 // exchange itself belongs to the host (LAMMPS CommBrick through
 // pack/unpack_*_comm_gnn, row maps in CommMaps below): the step exposes the row
 // buffer `comm_rows()` = [graph rows | extra rows | zero row | trash rows].
@@ -156,7 +162,7 @@ class ParallelStep {
   int unpack(const int32_t* idx, int64_t n, const float* buf, bool accumulate);
   // one evaluation: forward with `ex.forward` between the blocks, backward
   // with `ex.reverse` after each block and for the ghost forces
-  int compute(Exchange& ex, double** f, double* eatom, PairOut& out);
+  int compute(Exchange& ex, double** f, double* eatom, PairOut& out, double** vatom = nullptr);
   const std::string& error() const { return err_; }
   void* stream() const { return stream_; }
 
@@ -170,7 +176,7 @@ class ParallelStep {
   DeviceGraph g_;
   int64_t nlocal_ = 0, nghost_graph_ = 0;
   std::vector<int32_t> type_, center_, nbr_;
-  std::vector<float> vec_, forces_, atomic_;
+  std::vector<float> vec_, forces_, atomic_, vatom_;
   std::vector<int> row_to_i_;          // graph row -> LAMMPS atom index
   std::vector<int> i_to_row_;          // LAMMPS atom index -> graph row (-1)
   std::vector<int> tag_to_row_;        // tag -> graph row (-1)

@@ -48,6 +48,7 @@ SIGNATURES = {
     'e3gnn_layer_backward_part': (_c_int, [_vp, _c_int, _c_int, _vp]),
     'e3gnn_grad_ptr': (_vp, [_vp, _c_int]),
     'e3gnn_forces': (_c_int, [_vp, _vp, _vp, _vp, _vp]),
+    'e3gnn_atom_virial': (_c_int, [_vp, _vp, _vp]),
     'e3gnn_halo_pack': (_c_int, [_vp, _c_i64, _c_int, _vp, _c_i64, _vp, _vp]),
     'e3gnn_halo_unpack': (_c_int, [_vp, _c_i64, _c_int, _vp, _vp, _c_i64, _c_int, _vp]),
     'e3gnn_conv_dims': (_c_int, [_c_int, _P(_c_int), _P(_c_int), _P(_c_int)]),

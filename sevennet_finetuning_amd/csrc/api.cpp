@@ -22,6 +22,7 @@
 
 #include "../../include/e3gnn.h"
 #include "api_util.h"
+#include "atom_virial.h"
 #include "cg_tables.h"
 #include "common.h"
 #include "dbuf.h"
@@ -72,7 +73,7 @@ struct Pending {
 const char* kClassNames[] = {"graph_build", "edge_embed",  "node_linear", "radial_mlp_fwd",
                              "tp_fwd",      "gate_fwd",    "readout",     "gate_bwd",
                              "tp_bwd",      "radial_mlp_bwd", "gather_src", "edge_force",
-                             "atom_force",  "embed",
+                             "atom_force",  "atom_virial", "embed",
                              // fused kernels, one class per kernel and block kind
                              "conv_fwd.first", "conv_fwd.mid", "conv_fwd.last",
                              "conv_bwd_x.first", "conv_bwd_x.mid", "conv_bwd_x.last"};
@@ -90,6 +91,7 @@ enum Cls {
   C_GATHER,
   C_EDGE_FORCE,
   C_ATOM_FORCE,
+  C_ATOM_VIRIAL,
   C_EMBED_NODE,
   C_CONV_FWD,             // + kind (0 first, 1 mid, 2 last)
   C_CONV_BWD_X = C_CONV_FWD + 3,
@@ -140,6 +142,9 @@ struct e3gnn_ctx {
   std::vector<Pending> pending;
   std::vector<hipEvent_t> evpool;
   int readout_done = 0;
+  // e3gnn_forces has written the per-edge dE/dr of the current graph (what
+  // e3gnn_atom_virial reads); cleared by e3gnn_graph_set
+  int forces_done = 0;
 
   hipEvent_t ev() {
     if (!evpool.empty()) {
@@ -406,6 +411,7 @@ int e3gnn_graph_set(e3gnn_ctx* c, int64_t n_local, int64_t n_ghost, int64_t n_ed
                     const int32_t* type, const int32_t* edge_center, const int32_t* edge_nbr,
                     const float* edge_vec, void* stream) {
   if (!c) return fail(E3GNN_ERR_ARG, "null context");
+  c->forces_done = 0;
   if (n_local < 0 || n_ghost < 0 || n_edges < 0) return fail(E3GNN_ERR_ARG, "negative size");
   if (n_local + n_ghost > (1LL << 30) || n_edges > (1LL << 31) - 1)
     return fail(E3GNN_ERR_ARG, "graph too large for int32 indices");
@@ -936,6 +942,7 @@ int e3gnn_forces(e3gnn_ctx* c, float* forces, float* virial6, float* edge_grad, 
   hipStream_t s = (hipStream_t)stream;
   if (c->gen) {
     HIPCHK(gen_forces(c->gen, m->gen, gen_graph(c), forces, virial6, edge_grad, s));
+    c->forces_done = 1;
     return E3GNN_OK;
   }
   const int64_t n = c->n, nl = c->nl, E = c->E;
@@ -953,6 +960,34 @@ int e3gnn_forces(e3gnn_ctx* c, float* forces, float* virial6, float* edge_grad, 
   }
   if (edge_grad && E > 0)
     HIPCHK(hipMemcpyAsync(edge_grad, c->fe.p, E * 12, hipMemcpyDeviceToDevice, s));
+  c->forces_done = 1;
+  return E3GNN_OK;
+}
+
+int e3gnn_atom_virial(e3gnn_ctx* c, float* atom_virial6, void* stream) {
+  if (!c) return fail(E3GNN_ERR_ARG, "null context");
+  if (!atom_virial6) return fail(E3GNN_ERR_ARG, "null atom_virial6 output");
+  if (!c->forces_done)
+    return fail(E3GNN_ERR_ARG, "e3gnn_forces (or e3gnn_energy_forces) on the current graph must "
+                               "precede e3gnn_atom_virial");
+  HIPCHK(hipSetDevice(c->m->device));
+  hipStream_t s = (hipStream_t)stream;
+  // stream-ordered mode: the per-edge dE/dr is ready at the end of the last
+  // evaluation (done_ev), and a later graph_set on another stream must not
+  // overwrite it under this launch (done_ev moves behind it)
+  const bool ordered = c->done_pending;
+  if (ordered && c->done_stream != s) HIPCHK(hipStreamWaitEvent(s, c->done_ev, 0));
+  const float* fe = c->gen ? gen_fe(c->gen) : c->fe.f();
+  {
+    // both index lists, edge_vec and dE/dr once per edge end; one row out
+    Region r(c, s, C_ATOM_VIRIAL, 18.0 * 2 * c->E, (double)c->E * 4 * 2 * 7 + c->n * 24.0);
+    HIPCHK(launch_atom_virial((int)c->n, (int)c->nl, c->row_ptr.i(), c->src_ptr.i(),
+                              c->src_perm.i(), c->vec.f(), fe, atom_virial6, s));
+  }
+  if (ordered) {
+    HIPCHK(hipEventRecord(c->done_ev, s));
+    c->done_stream = s;
+  }
   return E3GNN_OK;
 }
 

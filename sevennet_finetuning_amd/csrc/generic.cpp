@@ -565,6 +565,7 @@ GenCtx* gen_ctx_create(const GenModel* m) {
 void gen_ctx_free(GenCtx* c) { delete c; }
 float* gen_x(GenCtx* c, int layer) { return c->x[layer].f(); }
 float* gen_grad(GenCtx* c, int layer) { return c->grad[layer].f(); }
+const float* gen_fe(const GenCtx* c) { return static_cast<const float*>(c->fe.p); }
 
 hipError_t gen_graph_set(GenCtx* c, const GenModel* m, const GenGraph& g, hipStream_t s) {
   const size_t F = sizeof(float);

@@ -84,6 +84,7 @@ GenCtx* gen_ctx_create(const GenModel* m);
 void gen_ctx_free(GenCtx* c);
 float* gen_x(GenCtx* c, int layer);
 float* gen_grad(GenCtx* c, int layer);
+const float* gen_fe(const GenCtx* c);  // per-edge dE/dr of the last gen_forces
 
 // every call returns hipSuccess or the first failing HIP status
 hipError_t gen_graph_set(GenCtx* c, const GenModel* m, const GenGraph& g, hipStream_t s);

@@ -28,6 +28,25 @@ from . import _lib
 ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'assets')
 
 
+def atom_virial_partition(n, edge_center, edge_nbr, edge_vec, edge_grad):
+    """Per-atom virial ``[n, 6]`` (xx, yy, zz, xy, yz, zx) of the edge-gradient
+    partition in torch: every edge's virial term ``-voigt(r_e, dE/dr_e)``
+    (symmetrised, as ``k_edge_force`` forms it) goes in halves to its centre
+    and its neighbour, so an edge to the atom's own image gives it both halves
+    and the rows sum to the total virial.  What ``e3gnn_atom_virial``
+    computes on the device (csrc/atom_virial.hip), for the autograd engine
+    and the host-graph paths; not a centroid stress."""
+    r, g = edge_vec, edge_grad.to(edge_vec.dtype)
+    v = -torch.stack([r[:, 0] * g[:, 0], r[:, 1] * g[:, 1], r[:, 2] * g[:, 2],
+                      0.5 * (r[:, 0] * g[:, 1] + r[:, 1] * g[:, 0]),
+                      0.5 * (r[:, 1] * g[:, 2] + r[:, 2] * g[:, 1]),
+                      0.5 * (r[:, 0] * g[:, 2] + r[:, 2] * g[:, 0])], dim=1)
+    w = torch.zeros(int(n), 6, dtype=v.dtype, device=v.device)
+    w.index_add_(0, edge_center.long(), 0.5 * v)
+    w.index_add_(0, edge_nbr.long(), 0.5 * v)
+    return w
+
+
 class E3GNNModel:
     """A loaded deployment (weights.bin + manifest.json) on one HIP device."""
 
@@ -91,9 +110,13 @@ class E3GNNModel:
     def stream_handle(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def energy_forces(self, types, edge_center, edge_nbr, edge_vec, want_edge_grad=False):
+    def energy_forces(self, types, edge_center, edge_nbr, edge_vec, want_edge_grad=False,
+                      want_atom_virial=False):
         """One evaluation on device tensors (int32 types/centre/nbr, fp32 vec E x 3),
-        edge_center sorted non-decreasing.  Returns dict of device tensors."""
+        edge_center sorted non-decreasing.  Returns dict of device tensors;
+        ``want_atom_virial`` adds ``atomic_virial`` [n, 6] (xx, yy, zz, xy, yz,
+        zx), the edge-gradient partition of ``virial`` (e3gnn_atom_virial: one
+        more launch, none without it)."""
         dev = self.device
         n = int(types.shape[0])
         E = int(edge_center.shape[0])
@@ -114,6 +137,10 @@ class E3GNNModel:
         out = {'energy': energy[0], 'atomic_energy': eat, 'forces': forces, 'virial': virial}
         if egrad is not None:
             out['edge_grad'] = egrad
+        if want_atom_virial:
+            w = torch.empty(n, 6, device=dev)
+            _lib.check(self.lib.e3gnn_atom_virial(self._ctx, w.data_ptr(), self.stream_handle()))
+            out['atomic_virial'] = w
         return out
 
     def set_impl(self, impl):
@@ -262,7 +289,8 @@ class GenericE3GNNModel:
     def set_is_batch_data(self, flag: bool):
         self.is_batch_data = bool(flag)
 
-    def energy_forces(self, types, edge_center, edge_nbr, edge_vec, want_edge_grad=False):
+    def energy_forces(self, types, edge_center, edge_nbr, edge_vec, want_edge_grad=False,
+                      want_atom_virial=False):
         dev = self.device
         n = int(types.shape[0])
         ei = torch.stack([edge_center.to(dev).long(), edge_nbr.to(dev).long()])
@@ -278,6 +306,9 @@ class GenericE3GNNModel:
                'virial': out[KEY.PRED_STRESS].detach().view(6)}
         if want_edge_grad:
             raise _lib.E3GNNError('edge gradients are exposed by the SevenNet-0 engine only')
+        if want_atom_virial:   # the same partition from autograd's edge gradient
+            res['atomic_virial'] = atom_virial_partition(
+                n, ei[0], ei[1], out[KEY.EDGE_VEC].detach(), out[KEY.EDGE_GRAD].detach())
         return res
 
     def __call__(self, data):

@@ -686,6 +686,8 @@ class SevenNetTrainable(torch.nn.Module):
         force = torch.zeros(n, 3, device=dev, dtype=fij.dtype).index_add(
             0, torch.cat([src, dst]), torch.cat([fij, -fij]))
         out[KEY.PRED_FORCE] = force
+        if not self.training:   # dE/dr per edge, for the per-atom virial (model.atom_virial_partition)
+            out[KEY.EDGE_GRAD] = fij
         # virial terms xx yy zz xy yz zx = r_a f_b for (a, b) = (x,x) .. (z,x),
         # summed per graph straight from the edges (graph of the edge's dst atom)
         voigt = vec.repeat(1, 2) * torch.cat([fij, fij.roll(-1, dims=1)], dim=1)

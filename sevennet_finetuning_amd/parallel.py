@@ -40,7 +40,9 @@ Here, one process per GPU:
 * ``ParallelE3GNN.set_graph`` uploads a rank graph once per neighbour list;
   ``evaluate`` runs one evaluation: graph_set, 5 x (halo forward, layer
   forward), readout, 5 x (layer backward, halo reverse), forces, reverse of
-  the ghost forces, one all_reduce of (energy, virial).
+  the ghost forces, one all_reduce of (energy, virial).  ``atom_virial=True``
+  adds the per-atom virial (e3gnn_atom_virial) and one more reverse exchange
+  that brings the ghost rows' halves home, exactly as the ghost forces go.
 
 The per-rank compute is an *engine* with the segment interface of
 include/e3gnn.h (``HipSegmentEngine`` wraps libe3gnn_hip.so; tests plug in a
@@ -489,6 +491,7 @@ class HipSegmentEngine:
         self.device = model.device
         self.num_layers = model.num_layers
         self._forces = None
+        self._atom_virial = None
 
     def _s(self):
         return self.m.stream_handle()
@@ -523,7 +526,9 @@ class HipSegmentEngine:
                                             v.data_ptr(), self._s()))
 
     def dim(self, kind, t):
-        return 3 if kind == 'force' else self.lib.e3gnn_feature_dim(self.ctx, t)
+        if kind in ('force', 'atom_virial'):
+            return 3 if kind == 'force' else 6
+        return self.lib.e3gnn_feature_dim(self.ctx, t)
 
     def empty(self, n, dim):
         return torch.empty(n, dim, dtype=torch.float32, device=self.device)
@@ -533,6 +538,8 @@ class HipSegmentEngine:
             return self.lib.e3gnn_feature_ptr(self.ctx, t)
         if kind == 'grad':
             return self.lib.e3gnn_grad_ptr(self.ctx, t)
+        if kind == 'atom_virial':
+            return self._atom_virial.data_ptr()
         return self._forces.data_ptr()
 
     def pack(self, kind, t, idx, out):
@@ -573,6 +580,13 @@ class HipSegmentEngine:
         _lib.check(self.lib.e3gnn_forces(self.ctx, self._forces.data_ptr(), vir.data_ptr(),
                                          None, self._s()))
         return self._forces, vir
+
+    def atom_virial(self):
+        """Per-atom virial of all owned + ghost rows after ``forces`` (buffer
+        kind 'atom_virial', width 6: ghost rows go back to their owners)."""
+        self._atom_virial = torch.empty(max(self.n, 1), 6, device=self.device)
+        _lib.check(self.lib.e3gnn_atom_virial(self.ctx, self._atom_virial.data_ptr(), self._s()))
+        return self._atom_virial
 
 
 # ------------------------------------------------------------------ driver
@@ -634,10 +648,13 @@ class ParallelE3GNN:
         timing['exchanges'] = timing.get('exchanges', 0) + 1
         return h
 
-    def evaluate(self, timing=None):
+    def evaluate(self, timing=None, atom_virial=False):
         """One evaluation.  ``timing``: a dict to fill with the wall time of
         the halo exchanges run serially (no overlap; see ``_exchange``) and of
-        the whole evaluation, so compute = total - exchange."""
+        the whole evaluation, so compute = total - exchange.  ``atom_virial``:
+        also the per-atom virial of the owned rows (``'atomic_virial'``,
+        [n_local, 6] in xx yy zz xy yz zx), at the cost of one more launch and
+        one more reverse exchange after the ghost forces'."""
         eng, halo, L = self.eng, self.halo, self.eng.num_layers
         t_begin = time.perf_counter()
         eng.graph_set()
@@ -666,6 +683,13 @@ class ParallelE3GNN:
         # ghost forces -> owners (newton on)
         halo.reverse_finish(self._exchange(halo.reverse_start, halo.reverse_finish, 'force', 0,
                                            timing))
+        w = None
+        if atom_virial:
+            # ghost rows hold the neighbour-side halves of the edges other
+            # ranks own: they go to their owners like the ghost forces
+            w = eng.atom_virial()
+            halo.reverse_finish(self._exchange(halo.reverse_start, halo.reverse_finish,
+                                               'atom_virial', 0, timing))
         tot = torch.cat([e_local.reshape(1), vir.reshape(6)]).to(torch.float64)
         if dist.is_initialized() and self.rg.world > 1:
             if self._comm_device() == 'cpu' and tot.device.type != 'cpu':
@@ -678,8 +702,11 @@ class ParallelE3GNN:
             self._sync()
             timing['total_s'] = time.perf_counter() - t_begin
         nl = self.rg.n_local
-        return {'energy': tot[0], 'virial': tot[1:7], 'forces': forces[:nl],
-                'atomic_energy': atomic, 'owned': self.rg.owned}
+        res = {'energy': tot[0], 'virial': tot[1:7], 'forces': forces[:nl],
+               'atomic_energy': atomic, 'owned': self.rg.owned}
+        if w is not None:
+            res['atomic_virial'] = w[:nl]
+        return res
 
 
 def gather_all(res, n_atoms, group=None, device='cpu'):

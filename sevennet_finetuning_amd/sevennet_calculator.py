@@ -2,6 +2,10 @@
 (sevenn/sevennet_calculator.py:17-157): same constructor arguments, same
 ``results`` keys (energy, free_energy, energies, forces, stress) and the same
 ASE stress convention (-sigma in Voigt order xx yy zz yz xz xy, :151-156).
+Beyond the reference: ``stresses`` (ASE's per-atom stress, [n, 6] in the same
+order, sign and 1/V as ``stress``, so ``stresses.sum(0) == stress``), computed
+only when ``properties`` asks for it.  It is the edge-gradient partition of
+the virial ("Per-atom virial"), not a centroid stress.
 
 ASE is optional: when importable the class derives from
 ``ase.calculators.calculator.Calculator``; otherwise it duck-types the parts
@@ -63,7 +67,8 @@ class SevenNetCalculator(Calculator):
         self.type_map = self.model.type_map()
         self.cutoff = self.model.cutoff
         self.sevennet_config = sevennet_config
-        self.implemented_properties = ['free_energy', 'energy', 'forces', 'stress', 'energies']
+        self.implemented_properties = ['free_energy', 'energy', 'forces', 'stress', 'energies',
+                                       'stresses']
         self._nlist = None
 
     def _types(self, atoms):
@@ -72,7 +77,7 @@ class SevenNetCalculator(Calculator):
         except KeyError as e:
             raise ValueError(f'atomic number {e} is not a species of this model') from None
 
-    def _calculate_device_graph(self, atoms):
+    def _calculate_device_graph(self, atoms, want_stresses=False):
         """Graph built by the device neighbour list (periodic or isolated
         systems): positions go to the GPU once, nothing comes back until the
         results."""
@@ -84,7 +89,8 @@ class SevenNetCalculator(Calculator):
         center, nbr, _, vec = self._nlist(atoms.get_positions(), cell if pbc else None,
                                           self.cutoff, (pbc,) * 3)
         types = torch.as_tensor(self._types(atoms), dtype=torch.int32, device=self.device)
-        res = self.model.energy_forces(types, center, nbr, vec)
+        kw = {'want_atom_virial': True} if want_stresses and pbc else {}
+        res = self.model.energy_forces(types, center, nbr, vec, **kw)
         energy = float(res['energy'].item())
         self.results = {
             'free_energy': energy,
@@ -95,6 +101,9 @@ class SevenNetCalculator(Calculator):
         if pbc:
             sigma = res['virial'].cpu().numpy() / abs(np.linalg.det(cell))
             self.results['stress'] = -sigma[[0, 1, 2, 4, 5, 3]]
+            if want_stresses:
+                w = res['atomic_virial'].cpu().numpy() / abs(np.linalg.det(cell))
+                self.results['stresses'] = -w[:, [0, 1, 2, 4, 5, 3]]
         return res
 
     def calculate(self, atoms=None, properties=None, system_changes=all_changes):
@@ -102,8 +111,9 @@ class SevenNetCalculator(Calculator):
         if atoms is None:
             raise ValueError('No atoms to evaluate')
         pbc = np.asarray(atoms.get_pbc(), dtype=bool).reshape(-1)
+        want_stresses = properties is not None and 'stresses' in properties
         if pbc.all() or not pbc.any():
-            return self._calculate_device_graph(atoms)
+            return self._calculate_device_graph(atoms, want_stresses)
         # mixed periodicity (slabs): the host list (util.unlabeled_atoms_to_graph)
         data = unlabeled_atoms_to_graph(atoms, self.cutoff)
         data[KEY.NODE_FEATURE] = self._types(atoms)
@@ -118,6 +128,13 @@ class SevenNetCalculator(Calculator):
         if KEY.PRED_STRESS in out:
             self.results['stress'] = np.array(
                 (-out[KEY.PRED_STRESS]).detach().cpu().numpy()[[0, 1, 2, 4, 5, 3]])
+            if want_stresses:   # the torch partition of the host graph's edge gradient
+                from .model import atom_virial_partition
+                g = out[KEY.EDGE_GRAD].detach()
+                ei = torch.as_tensor(data[KEY.EDGE_IDX], device=g.device)
+                vec = torch.as_tensor(data[KEY.EDGE_VEC], dtype=torch.float32, device=g.device)
+                w = atom_virial_partition(len(atoms), ei[0], ei[1], vec, g).cpu().numpy()
+                self.results['stresses'] = -w[:, [0, 1, 2, 4, 5, 3]] / abs(data[KEY.CELL_VOLUME])
 
 
 class SevenNetD3Calculator(Calculator):
@@ -125,7 +142,8 @@ class SevenNetD3Calculator(Calculator):
     ``pair_style hybrid/overlay e3gnn d3 <rthr> <cn_thr> <damping> <functional>``
     (the reference's pair_e3gnn.cpp + pair_d3.cu), i.e. energies, forces and
     stresses of the two terms summed.  Per-atom energies are the SevenNet
-    ones (the D3 term is not atom-decomposed, as in pair_d3.cu)."""
+    ones (the D3 term is not atom-decomposed, as in pair_d3.cu); for the same
+    reason there is no per-atom ``stresses`` here."""
 
     def __init__(self, model='SevenNet-0', file_type='checkpoint', device='auto',
                  damping_type='damp_bj', functional_name='pbe', vdw_cutoff=9000.0,
@@ -140,6 +158,8 @@ class SevenNetD3Calculator(Calculator):
 
     def calculate(self, atoms=None, properties=None, system_changes=all_changes):
         a = self.sevennet
+        if properties is not None:   # no per-atom D3 virial to add to it
+            properties = [p for p in properties if p != 'stresses']
         a.calculate(atoms, properties, system_changes)
         b = self.d3.calculate(atoms)
         r = dict(a.results)
