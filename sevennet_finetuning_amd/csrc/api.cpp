@@ -906,6 +906,10 @@ int e3gnn_layer_backward_part(e3gnn_ctx* c, int t, int part, void* stream) {
   // part 0: boundary centres / their edges / ghost neighbour nodes
   a.c_begin = (int)(part == 0 ? n_int : 0);
   a.c_end = (int)(part == 0 ? nl : n_int);
+  // (graph_set checked every centre to lie in [0, nl): row_ptr[nl] == E, and
+  // e_int is row_ptr[n_int])
+  a.e_begin = (int)(part == 0 ? e_int : 0);
+  a.e_end = (int)(part == 0 ? E : e_int);
   a.node_begin = (int)(part == 0 ? nl : 0);
   a.node_end = (int)(part == 0 ? n : nl);
   double ef = (double)(part == 0 ? E - e_int : e_int);

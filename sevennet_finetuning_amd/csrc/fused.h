@@ -59,12 +59,16 @@ struct FusedArgs {
   // centres [c_begin, c_end) (forward, first / middle backward), neighbour
   // nodes [node_begin, node_end) (last backward)
   int c_begin, c_end, node_begin, node_end;
+  // the CSR edges of the centre range, [row_ptr[c_begin], row_ptr[c_end]): the
+  // first / middle backward partitions its launch by edges
+  int e_begin, e_end;
 };
 
 // `kind` is a kind code of tp.h (3 * channel family + block kind)
 hipError_t launch_conv_fwd(int kind, const FusedArgs& a, hipStream_t s);
-// backward of a first / middle block: the lock-step kernel (4 centres per
-// workgroup, W2 operands staged per block pair in LDS, dH2 on bf16x6), per-edge
+// backward of a first / middle block: the lock-step kernel (rounds of four
+// consecutive 16-edge tiles of the range [e_begin, e_end) per workgroup, W2
+// operands staged per block pair in LDS, dH2 on bf16x6), per-edge
 // dE/dx to dxc, dE/du, dE/dw -> dE/demb
 hipError_t launch_conv_bwd_ls(int kind, const FusedArgs& a, hipStream_t s);
 // backward of the last block, one wave per neighbour node: dE/dx to dh, dE/du,

@@ -20,8 +20,9 @@
 //   * Forward: w = H2 W2[:, 16-column block], lane (g, c) holds w[edge 4g+r]
 //     [channel c]; two tiles per pass share every W2 operand block; the
 //     message is summed over registers and the 4 lane groups into the
-//     centre's row in LDS.  Backward (lock-step, 4 centres per workgroup, W2
-//     pieces staged per block pair in LDS): w^T recomputed, lane (g, c) =
+//     centre's row in LDS.  Backward (lock-step, four consecutive 16-edge
+//     tiles per round whatever their centres, W2 pieces staged per block
+//     pair in LDS): w^T recomputed, lane (g, c) =
 //     edge c x channels 4g..4g+3; dE/dx per edge, dE/dY -> dE/du, dE/dw ->
 //     dH2 (bf16x6 over the pair) -> MLP chain -> dE/demb.
 //   * Weights via buffer descriptors (scalar k offsets, one VGPR of lane offset).
@@ -1243,8 +1244,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 // ================================================================ lock-step kernels
-// One workgroup = 4 waves = 4 consecutive centres (one wave per centre, its
-// CSR edges in 16-edge tiles, tile t of the four centres at the same time).
+// One workgroup = 4 waves over a contiguous range of the launch's CSR edges,
+// walked in ROUNDS of four consecutive 16-edge tiles (one per wave, in
+// lock-step).  Every output is per edge and no sum crosses edges, so a tile
+// need not belong to one centre: it takes its lanes' centres from center[] and
+// their dE/dagg rows from a window of four LDS slots (centre c in slot c & 3),
+// and a round spans at most four consecutive centres (its edges end at
+// row_ptr[cf + 4], cf the centre of its first edge: low-degree graphs).  No
+// slot of a tile is padding except at a round's clipped end.
 // The waves walk the same sequence of 16-column weight blocks and share the
 // W2 operands of each block PAIR: staged once per workgroup in LDS (register
 // staging: issued a whole pair ahead, written between two barriers), so each
@@ -1325,33 +1332,36 @@ __device__ __forceinline__ void dh2_pair(f32x4 (&dh2)[4], const float (&da)[4], 
   }
 }
 
-// tiles of the workgroup's centres [cb, cb + 4) clipped to c_end: the lock-step
-// loop count
-__device__ __forceinline__ int ls_tiles(const int* __restrict__ row_ptr, int cb, int c_end) {
-  int T = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const int cc = cb + w;
-    if (cc < c_end) T = max(T, (row_ptr[cc + 1] - row_ptr[cc] + 15) >> 4);
-  }
-  return __builtin_amdgcn_readfirstlane(T);
-}
+// full rounds (64 edges) of a workgroup's edge range: a range re-stages the
+// row of the centre it starts in and pays one staging latency at its start.
+// 8, 4 and 2 measured the same step time on the Si benchmark box (5.3k, 10.6k
+// and 21.3k workgroups over 512 resident slots)
+constexpr int LS_ROUNDS = 8;
+// floats between two centres' staged dE/dagg rows: the row, skewed so that the
+// stride is 64 B modulo the 256 B of the LDS banks.  A tile that spans centres
+// reads the same row offset in up to four slots at once; with the slots 16
+// banks apart, the 16-byte windows of (slot s, lane group g) and (s', g') are
+// disjoint for D3 = 1, 3, 5 (4 (s - s') + D3 (g - g') is never 0 modulo 16 for
+// |s - s'|, |g - g'| <= 3 unless both are 0).  Unskewed, SevenNet-0's middle row
+// (12,032 B = 47 x 256) puts every slot on the same banks.
+constexpr int ls_row_stride(int dms) { return dms + ((64 - dms * 4 % 256 + 256) % 256) / 4; }
 
 // Backward of a first / middle block (per-edge dE/dx to dxc, summed per
 // neighbour by the transposed-CSR gather; dE/dY -> dE/du; dE/dw -> dH2 -> MLP
-// chain -> dE/demb), the centre's dE/dagg row staged in LDS once.  Same pair
+// chain -> dE/demb), each centre's dE/dagg row staged in LDS once per
+// workgroup range (the four-slot window above).  Same pair
 // structure as the forward (both blocks' w formed at the pair start, next
 // group's neighbour rows prefetched); dH2 of the pair on bf16x6 at its end.
 // waves per SIMD: the first block (128 input channels, 1,152 message channels:
 // 34.8 KB of LDS per workgroup, two images) runs three (168 VGPRs with a few
 // spills measured 2.57 -> 2.27 ms against two), the middle blocks two (their
-// 230-243 VGPRs allow no more; 64.5 KB of LDS per workgroup, 80.9 KB with
+// 241-254 VGPRs allow no more; 64.8 KB of LDS per workgroup, 81.2 KB with
 // two pairs per barrier, LsQuads below)
 template <class L>
 struct BwdLsWaves {
   static constexpr int v = L::KIND == 0 ? 3 : 2;
 };
-// centres (waves) per workgroup (one 8-wave workgroup per CU sharing each
+// tiles (waves) per round and workgroup (one 8-wave workgroup per CU sharing each
 // staged W2 pair, 124 KB of LDS, measured slower for the middle block)
 constexpr int LS_WPG = 4;
 // Double-buffered staging where two images fit (the middle blocks: backward
@@ -1373,7 +1383,7 @@ template <class L>
 struct LsTwoImages {
   static constexpr int OFF0 = L::KIND == 1 ? L::P[0].mul : 0;   // path 0 (l 0 0 0, moff 0): C0 floats
   static constexpr int DMS = L::DM - OFF0;                       // staged dE/dagg floats per centre
-  static constexpr int bytes = LS_WPG * DMS * 4 + 2 * LS_IMG;
+  static constexpr int bytes = LS_WPG * ls_row_stride(DMS) * 4 + 2 * LS_IMG;
   static constexpr bool v = BwdLsWaves<L>::v * bytes <= 163840;
 };
 // Two pairs per barrier: each of the two buffers holds the images of two
@@ -1382,7 +1392,7 @@ struct LsTwoImages {
 // position in its group of four to be a compile-time constant (the channel
 // groups of an input irrep unrolled until their blocks are a multiple of four)
 // and 4 images beside the staged rows at the kernel's workgroups per CU:
-// SevenNet-0's middle block (80,896 B, two per CU); c64's rows are too long,
+// SevenNet-0's middle block (81,152 B, two per CU); c64's rows are too long,
 // c32's l1 = 0 groups too few.  Step 37.64-38.06 -> 37.23-37.37 ms, launch 5.12 ->
 // 4.87 ms against one pair per barrier (profiles/quads_bench.log).  The same kernel at THREE waves
 // per SIMD (the l1 = 0 paths' dE/dagg from L2, 50.4 KB of LDS, 168 VGPRs) was
@@ -1396,7 +1406,7 @@ struct LsQuads {
       if (mul_of<L>(i) > 0 && (mul_of<L>(i) / 16 % unroll(paths_of<L>(i)) || blocks_before<L>(i) % 4)) return false;
     return true;
   }
-  static constexpr int bytes = LS_WPG * (L::DM - LsTwoImages<L>::OFF0) * 4 + 4 * LS_IMG;
+  static constexpr int bytes = LS_WPG * ls_row_stride(L::DM - LsTwoImages<L>::OFF0) * 4 + 4 * LS_IMG;
   static constexpr bool v = L::KIND == 1 && LsTwoImages<L>::v && pos_ok() && BwdLsWaves<L>::v * bytes <= 163840;
 };
 // wave priority, raised around the lock-step backward's MFMA bursts
@@ -1406,8 +1416,8 @@ template <class L>
 __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(BwdLsWaves<L>::v, BwdLsWaves<L>::v))) void k_conv_bwd_ls(
     const int* __restrict__ row_ptr, const int* __restrict__ nbr, const float* __restrict__ emb,
     const float* __restrict__ Y, const float* __restrict__ h, const float* __restrict__ gagg, MlpW W,
-    float* __restrict__ dxc, float* __restrict__ dgu, float* __restrict__ demb, int c_begin,
-    int c_end, int n_nodes) {
+    float* __restrict__ dxc, float* __restrict__ dgu, float* __restrict__ demb,
+    const int* __restrict__ center, int e_begin, int e_end, int c_end, int n_nodes) {
   constexpr int NBLK = L::W / 16, NPAIR = NBLK / 2;
   static_assert(NBLK % 2 == 0, "weight blocks come in pairs");
   constexpr int WPG = LS_WPG, NT = 64 * WPG;
@@ -1424,25 +1434,16 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
   constexpr int OFF0 = TWO ? LsTwoImages<L>::OFF0 : 0, DMS = L::DM - OFF0;   // dE/dagg floats staged per centre
   static_assert(!TWO || (L::P[0].l1 == 0 && L::P[0].l2 == 0 && L::P[0].l3 == 0 && L::P[0].moff == 0 &&
                          OFF0 % 4 == 0), "path 0 is the 0e x 0e -> 0e slice at the row start");
-  __shared__ __attribute__((aligned(16))) float smem[WPG * DMS + (TWO ? 2 : 1) * NIMG * LS_IMG / 4];
+  constexpr int RS = ls_row_stride(DMS);   // floats between two slots of the row window
+  __shared__ __attribute__((aligned(16))) float smem[WPG * RS + (TWO ? 2 : 1) * NIMG * LS_IMG / 4];
   const int tid = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, g = lane >> 4, col = lane & 15;
-  const int cb = c_begin + blockIdx.x * WPG;
-  const int c = cb + wid;
-  const bool valid = c < c_end;
-  const int beg = valid ? row_ptr[c] : 0, end = valid ? row_ptr[c + 1] : 0;
-  const int T = ls_tiles(row_ptr, cb, c_end);
-  float* dacc = smem + wid * DMS - OFF0;   // dacc[m] for m >= OFF0
-  char* img = reinterpret_cast<char*>(smem + WPG * DMS);
-  if (valid && end > beg) {
-    const float4* s4 = reinterpret_cast<const float4*>(gagg + (int64_t)c * L::DM + OFF0);
-    float4* d4 = reinterpret_cast<float4*>(dacc + OFF0);
-    for (int k = lane; k < DMS / 4; k += 64) d4[k] = s4[k];
-  }
-  // two images: the one the current pair reads (0 / 1), and path 0's dE/dagg
-  // row of this centre through a descriptor (invalid centres: empty, reads 0)
+  // the workgroup's edges [ws, we) of the launch's [e_begin, e_end)
+  const int ws = e_begin + blockIdx.x * (LS_ROUNDS * 16 * WPG);
+  const int we = min(ws + LS_ROUNDS * 16 * WPG, e_end);
+  char* img = reinterpret_cast<char*>(smem + WPG * RS);
+  int rhi = 0;   // centres below rhi have been staged (resident while in the window)
+  // two images: the one the current pair reads (0 / 1)
   int rb = 0;
-  const __amdgpu_buffer_rsrc_t Rg0 =
-      rsrc_bytes(gagg + (valid ? (int64_t)c * L::DM : 0), valid ? (int64_t)OFF0 * 4 : 0);
   const WRes R = make_wres(W, L::W);
   const __amdgpu_buffer_rsrc_t Rs = rsrc_bytes(W.w2s, NPAIR * w2img::PAIR_BYTES);   // the pair images
   const __amdgpu_buffer_rsrc_t Rx = rsrc_bytes(h, (int64_t)n_nodes * L::DX * 4);
@@ -1462,11 +1463,28 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
   constexpr bool STAMPED = std::is_same<L, LayerMid>::value && !E3GNN_STAMPS_FWD;   // SevenNet-0's
   STAMP_DECL
   issue(0);
-  for (int t = 0; t < T; ++t) {
+  for (int qr = ws; qr < we;) {
     if constexpr (STAMPED) STAMP(0);
-    const int q0 = beg + 16 * t;
+    // the round: edges [qr, end) of the centres cf .. cl (at most cf + 3)
+    const int cf = __builtin_amdgcn_readfirstlane(center[qr]);
+    const int end = __builtin_amdgcn_readfirstlane(min(min(qr + 16 * WPG, we), row_ptr[min(cf + 4, c_end)]));
+    const int cl = __builtin_amdgcn_readfirstlane(center[end - 1]);
+    // rows of the window not yet resident: cs0 .. cl (at most four)
+    const int cs0 = max(cf, rhi), nnew = cl - cs0 + 1;
+    rhi = cl + 1;
+    const int q0 = qr + 16 * wid;
+    qr = end;
     const bool act = q0 < end;   // wave-uniform
     const int er = (act && q0 + col < end) ? q0 + col : -1;
+    // the lane's centre: its dE/dagg row (dacc[m] for m >= OFF0) in slot
+    // centre & 3; path 0's slice (two images) through a descriptor over the
+    // round's rows, the lane's row relative to cf (absolute byte offsets pass
+    // 32 bits on large boxes)
+    const int dc = er >= 0 ? center[er] - cf : 0;
+    const float* dacc = smem + ((cf + dc) & 3) * RS - OFF0;
+    const __amdgpu_buffer_rsrc_t Rg0 = rsrc_bytes(
+        gagg + (int64_t)cf * L::DM, OFF0 > 0 ? ((int64_t)(cl - cf) * L::DM + OFF0) * 4 : 0);
+    const int vg0 = (dc * L::DM + 4 * g) * 4;
     const int vx = (er >= 0 ? nbr[er] : 0) * L::DX * 4;
     float xpf[20];   // the lane's 4 channels x D1 of the next channel group
     float g0pf[4];   // two images: path 0's dE/dagg of that group (l1 = 0 groups)
@@ -1474,7 +1492,7 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
       constexpr int D1q = 2 * Iq + 1;
       constexpr int XOq = iblock_xoff<L, Iq>();
       ldv<4 * D1q>(Rx, vx + 4 * g * D1q * 4, (XOq + 16 * jq * D1q) * 4, xpf);
-      if constexpr (OFF0 > 0 && Iq == 0) ldv<4>(Rg0, 4 * g * 4, 16 * jq * 4, g0pf);
+      if constexpr (OFF0 > 0 && Iq == 0) ldv<4>(Rg0, vg0, 16 * jq * 4, g0pf);
     };
     float y[9];
     // KEEP: old values of the tile end's read-modify-writes, and the tile's
@@ -1494,10 +1512,10 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
     const __amdgpu_buffer_rsrc_t Rd =
         rsrc_bytes(dxc ? dxc + (int64_t)(act ? q0 : 0) * L::DX : gagg, (int64_t)nrow * L::DX * 4);
     const int vd = col * L::DX * 4;
+    float b[2];
     if (act) {
 #pragma unroll
       for (int q = 0; q < 9; ++q) y[q] = er >= 0 ? Y[(int64_t)er * 9 + q] : 0.f;
-      float b[2];
 #pragma unroll
       for (int s = 0; s < 2; ++s) b[s] = er >= 0 ? emb[(int64_t)er * 8 + 4 * s + g] : 0.f;
       if constexpr (KEEP) {
@@ -1512,6 +1530,30 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
           for (int k = 0; k < 4; ++k) de_old[k] = demb[(int64_t)er * 8 + 4 * g + k];
         }
       }
+    }
+    // The window's new rows are copied with the tile's edge loads in flight
+    // (one exposed latency for both), every row's pieces requested before the
+    // first is written.  The barrier stands between every wave's last read of
+    // the rows they replace (the last barrier of a round is at its last
+    // group's start) and the writes; the round's first staging barrier
+    // publishes them.
+    {
+      constexpr int NRK = (DMS / 4 + NT - 1) / NT;   // b128 pieces of a row per thread
+      const __amdgpu_buffer_rsrc_t Rr = rsrc_bytes(
+          gagg + (int64_t)cs0 * L::DM + OFF0, nnew > 0 ? ((int64_t)(nnew - 1) * L::DM + DMS) * 4 : 0);
+      __syncthreads();
+      f32x4 rowv[4 * NRK];
+#pragma unroll
+      for (int i = 0; i < 4 * NRK; ++i)
+        rowv[i] = ldw4(Rr, ((i / NRK) * L::DM + (tid + NT * (i % NRK)) * 4) * 4, 0);
+#pragma unroll
+      for (int i = 0; i < 4 * NRK; ++i) {
+        const int k = tid + NT * (i % NRK);
+        if (i / NRK < nnew && k < DMS / 4)
+          reinterpret_cast<f32x4*>(smem + ((cs0 + i / NRK) & 3) * RS)[k] = rowv[i];
+      }
+    }
+    if (act) {
       MlpT m;
       mlp_chain<CX3>(R, b, lane, m);
       if constexpr (KEEP) {
@@ -1696,9 +1738,11 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
 
 template <class L>
 static hipError_t bwd_ls_impl(const FusedArgs& a, hipStream_t s) {
-  const int nc = a.c_end - a.c_begin;
-  hipLaunchKernelGGL(k_conv_bwd_ls<L>, dim3((nc + LS_WPG - 1) / LS_WPG), dim3(64 * LS_WPG), 0, s, a.row_ptr, a.nbr,
-                     a.emb, a.Y, a.h, a.gagg, a.W, a.dxc, a.dgu, a.demb, a.c_begin, a.c_end, a.n_nodes);
+  const int ne = a.e_end - a.e_begin, per = LS_ROUNDS * 16 * LS_WPG;   // edges per workgroup
+  if (ne <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_conv_bwd_ls<L>, dim3((ne + per - 1) / per), dim3(64 * LS_WPG), 0, s, a.row_ptr, a.nbr,
+                     a.emb, a.Y, a.h, a.gagg, a.W, a.dxc, a.dgu, a.demb, a.center, a.e_begin, a.e_end,
+                     a.c_end, a.n_nodes);
   return hipGetLastError();
 }
 

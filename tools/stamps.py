@@ -7,8 +7,14 @@ per wave, written to a buffer of their own; the shipped library has none).
 Builds nothing: the variant is made beforehand on the CPU with
 ``build_lib.build(out=..., defines=['E3GNN_STAMPS'])``.  Prints, over all
 waves of the last middle launch of one step, the share of wave cycles in
-each phase and the mean cycles per wave.  The stamps themselves cost ~10 %
-(each s_memtime waits for outstanding scalar/LDS operations).
+each phase and the mean cycles per wave.  A backward wave runs the rounds of
+its workgroup's edge range (fused.hip LS_ROUNDS, one 16-edge tile per round),
+so there are 4 waves per LS_ROUNDS x 64 edges; the line ``tiles`` relates the
+wave cycles to the 16-edge tiles of the launch (edges / 16, a lower bound of
+the tiles run, so the cycles per tile are an upper bound).  The forward has
+one wave per centre.  The stamps
+themselves cost ~10 % (each s_memtime waits for outstanding scalar/LDS
+operations).
 """
 import ctypes
 import os
@@ -54,6 +60,9 @@ def main():
     tot = a[:, 7].sum()
     print(f'waves {len(a)}, mean cycles/wave {a[:, 7].mean():.0f}, '
           f'max {a[:, 7].max():.0f}')
+    if names is PHASES:
+        tiles = (int(box['center'].numel()) + 15) // 16
+        print(f'tiles >= {tiles} (edges / 16), wave cycles per tile <= {tot / tiles:.0f}')
     for k in range(7):
         print(f'  {names[k]:18s} {a[:, k].sum() / tot:6.3f}   {a[:, k].mean():10.0f} cyc/wave')
     print(f'  unaccounted        {1 - a[:, :7].sum() / tot:6.3f}')
