@@ -187,6 +187,28 @@ int e3gnn_energy_forces(e3gnn_ctx* c, int64_t n_atoms, int64_t n_edges, const in
                         const int32_t* edge_center, const int32_t* edge_nbr,
                         const float* edge_vec, float* energy, float* atomic_energy,
                         float* forces, float* virial6, float* edge_grad, void* stream);
+/* The same evaluation on a batch of B graphs concatenated (the graph of
+ * e3gnn_nlist_batch_*; set_is_batch_data in sevenn/nn/sequential.py:38-46):
+ * structure s owns the atoms [atom_ptr[s], atom_ptr[s+1]) and no edge joins
+ * two structures.  atom_ptr: DEVICE int32 [B+1].  Outputs as above, except
+ * energy[B] and virial6[B][6] per structure: fixed-order sums (e3gnn_segment_sum)
+ * of the atomic energies and of e3gnn_atom_virial's rows -- no atomics, bitwise
+ * reproducible.  Serves every model e3gnn_energy_forces serves and honours the
+ * stream-ordered mode.  A NULL context, atom_ptr or energy and B < 1 are
+ * refused before any device work. */
+int e3gnn_energy_forces_batch(e3gnn_ctx* c, int64_t n_atoms, int64_t n_edges, int64_t B,
+                              const int32_t* atom_ptr, const int32_t* type,
+                              const int32_t* edge_center, const int32_t* edge_nbr,
+                              const float* edge_vec, float* energy, float* atomic_energy,
+                              float* forces, float* virial6, float* edge_grad, void* stream);
+/* out[s][c] = sum of in[r][c] over the rows r in [ptr[s], ptr[s+1]), for
+ * n_segments segments and width 1 or 6 (device arrays: ptr int32 [n_segments+1],
+ * in f32 [n_rows][width], out f32 [n_segments][width]; a range is clamped to
+ * [0, n_rows]).  One workgroup per segment, no atomics: the order of the
+ * additions depends on the segment's length and the width only.  Enqueued on
+ * `stream`. */
+int e3gnn_segment_sum(int64_t n_segments, const int32_t* ptr, int64_t n_rows, int width,
+                      const float* in, float* out, void* stream);
 
 /* ---- segment API (pair_e3gnn_parallel): one rank's local + ghost graph ---- */
 /* Nodes [0, n_local) are owned (edge centres), [n_local, n_local+n_ghost) are
@@ -538,6 +560,34 @@ int e3gnn_nlist_rank_build(e3gnn_nlist* h, int64_t n, const double* pos, const d
 int e3gnn_nlist_rank_fetch(e3gnn_nlist* h, int32_t* owned, int32_t* ghosts, int64_t* recv_counts,
                            int32_t* edge_center, int32_t* edge_nbr, int32_t* shift,
                            float* edge_vec, void* stream);
+
+/* Batched build (dataset inference: sevenn/scripts/inference.py:185-291 builds
+ * one graph per structure through AtomsToGraphCollater), on the same handle:
+ * B structures concatenated, one set of launches.  Structure s owns the rows
+ * [atom_ptr[s], atom_ptr[s+1]) of pos; its edges are those e3gnn_nlist_build
+ * gives for it alone -- same order, same integer shifts -- with atom_ptr[s]
+ * added to edge_center and edge_nbr, and the structures follow one another.
+ * atom_ptr: HOST int64 [B+1], atom_ptr[0] = 0, increasing (every structure has
+ * at least one atom); pos: DEVICE f64 [n][3], n = atom_ptr[B]; cells: HOST f64
+ * [B][3][3] (rows a, b, c; unread for an isolated structure, NULL if all are);
+ * periodic: HOST int32 [B], the periodic dimensions of each structure as bits
+ * (x = 1, y = 2, z = 4): 7 (periodic) or 0 (isolated cluster), anything else
+ * is refused.  e3gnn_nlist_batch_build counts the edges (synchronises `stream`
+ * once; isolated members cost one device-to-host copy of pos per batch);
+ * e3gnn_nlist_batch_fetch then writes edge_center / edge_nbr int32 [E], shift
+ * int32 [E][3], edge_vec f32 [E][3] and edge_ptr DEVICE int64 [B+1] (the edge
+ * range of each structure; shift, edge_vec and edge_ptr nullable).  Limits:
+ * B >= 1, n < 2^30, E < 2^31, at most 512 neighbours per centre and shifts
+ * within +-1024 cells, as above; a refusal names the structure where it is
+ * known.  The argument rules (NULL handle or arrays, B < 1, an empty or
+ * decreasing atom_ptr range, cutoff <= 0, a periodic value other than 0 or 7)
+ * are checked before any device work.  Every output is bitwise reproducible.
+ * Any build on a handle invalidates the fetches of the other builds. */
+int e3gnn_nlist_batch_build(e3gnn_nlist* h, int64_t B, const int64_t* atom_ptr, const double* pos,
+                            const double* cells, const int32_t* periodic, double cutoff,
+                            int64_t* n_edges, void* stream);
+int e3gnn_nlist_batch_fetch(e3gnn_nlist* h, int32_t* edge_center, int32_t* edge_nbr, int32_t* shift,
+                            float* edge_vec, int64_t* edge_ptr, void* stream);
 
 /* ---- DFT-D3 dispersion ----
  * Replaces the reference's LAMMPS pair style d3 (sevenn/pair_e3gnn/pair_d3.cu):

@@ -37,7 +37,9 @@ SIGNATURES = {
     'e3gnn_ctx_free': (None, [_vp]),
     'e3gnn_energy_forces': (_c_int, [_vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp]),
-    'e3gnn_graph_set': (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp]),
+    'e3gnn_energy_forces_batch': (_c_int, [_vp, _c_i64, _c_i64, _c_i64] + [_vp] * 10 + [_vp]),
+    'e3gnn_segment_sum': (_c_int, [_c_i64, _vp, _c_i64, _c_int, _vp, _vp, _vp]),
+    'e3gnn_graph_set':(_c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp]),
     'e3gnn_layer_forward': (_c_int, [_vp, _c_int, _vp]),
     'e3gnn_feature_ptr': (_vp, [_vp, _c_int]),
     'e3gnn_feature_dim': (_c_int, [_vp, _c_int]),
@@ -104,7 +106,10 @@ SIGNATURES = {
                                         _vp, _c_int, _c_int, _P(_c_i64), _P(_c_i64), _P(_c_i64),
                                         _P(_c_i64), _vp]),
     'e3gnn_nlist_rank_fetch': (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'e3gnn_set_impl': (_c_int, [_vp, _c_int]),
+    'e3gnn_nlist_batch_build': (_c_int, [_vp, _c_i64, _P(_c_i64), _vp, _P(ctypes.c_double),
+                                         _P(ctypes.c_int32), ctypes.c_double, _P(_c_i64), _vp]),
+    'e3gnn_nlist_batch_fetch': (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'e3gnn_set_impl':(_c_int, [_vp, _c_int]),
     'e3gnn_set_timing': (_c_int, [_vp, _c_int]),
     'e3gnn_set_stream_ordered': (_c_int, [_vp, _c_int]),
     'e3gnn_kernel_stats': (_c_int, [_vp, _P(_cp), _P(ctypes.c_double), _P(_c_i64),

@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, 'libe3gnn_hip.so')
 OBJDIR = os.path.join(HERE, 'csrc', 'build')
 SOURCES = ['api.cpp', 'model_load.cpp', 'api_train.cpp', 'api_nlist.cpp', 'api_d3.cpp', 'generic.cpp',
            'gemm.hip', 'tp.hip', 'node.hip', 'fused.hip', 'neighbor.hip', 'd3.hip', 'train_ops.hip', 'gtp.hip', 'generic.hip', 'mlp_train.hip', 'tgemm.hip',
-           'fcn_train.hip', 'atom_virial.hip']
+           'fcn_train.hip', 'atom_virial.hip', 'segment_sum.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', f'-I{INCLUDE}',
          '-Wall', '-Wno-unused-function']
@@ -91,7 +91,7 @@ def build(force=False, verbose=False, out=None, defines=()):
 NATIVE = os.path.join(os.path.dirname(HERE), 'native')
 
 
-NATIVE_HOSTS = ('e3gnn_md', 'e3gnn_md_parallel', 'e3gnn_pair_check')
+NATIVE_HOSTS = ('e3gnn_md', 'e3gnn_md_parallel', 'e3gnn_pair_check', 'e3gnn_batch_check')
 # extra translation units of a host (the LAMMPS pair-style core)
 NATIVE_EXTRA = {'e3gnn_pair_check': ['pair_e3gnn_core.cpp', 'lammps/pair_e3gnn_hip.cpp',
                                      'lammps/pair_e3gnn_parallel_hip.cpp', 'lammps_mock/mini_lammps.cpp']}
@@ -100,10 +100,12 @@ NATIVE_INCLUDES = {'e3gnn_pair_check': ['.', 'lammps_mock', 'lammps']}
 
 
 def build_native(lib=LIB, verbose=False, only_stale=False):
-    """native/e3gnn_md (serial MD host) and native/e3gnn_md_parallel (the
-    pair_e3gnn_parallel call sequence over N in-process sub-domains): C++ over
-    the C ABI (no Python), linked against the in-tree library with an
-    $ORIGIN-relative rpath."""
+    """native/e3gnn_md (serial MD host), native/e3gnn_md_parallel (the
+    pair_e3gnn_parallel call sequence over N in-process sub-domains),
+    native/e3gnn_pair_check (the LAMMPS adaptors in a scaffold) and
+    native/e3gnn_batch_check (the batched entry points): C++ over the C ABI
+    (no Python), linked against the in-tree library with an $ORIGIN-relative
+    rpath."""
     exes = []
     for name in NATIVE_HOSTS:
         srcs = [os.path.join(NATIVE, f) for f in [name + '.cpp'] + NATIVE_EXTRA.get(name, [])]

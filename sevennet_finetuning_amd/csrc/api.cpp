@@ -30,6 +30,7 @@
 #include "generic.h"
 #include "model.h"
 #include "node.h"
+#include "segment_sum.h"
 #include "tp.h"
 
 using namespace e3gnn;
@@ -130,6 +131,9 @@ struct e3gnn_ctx {
   // per layer
   std::vector<DBuf> x, grad, h, y, w, a1, a2;
   DBuf H1, H2, agg, dw, dxc, dy, dh, eat, part, vpart, scratch6;
+  // e3gnn_energy_forces_batch: atomic energies (when the caller takes none) and
+  // per-atom virials, the inputs of the per-structure sums
+  DBuf beat, bw;
   bool timing = false;
   bool stream_ordered = false;  // e3gnn_set_stream_ordered
   // stream-ordered mode: the end of the last evaluation on `done_stream`; a
@@ -1020,6 +1024,64 @@ int e3gnn_energy_forces(e3gnn_ctx* c, int64_t n_atoms, int64_t n_edges, const in
   return E3GNN_OK;
 }
 
+int e3gnn_segment_sum(int64_t n_segments, const int32_t* ptr, int64_t n_rows, int width,
+                      const float* in, float* out, void* stream) {
+  if (n_segments < 1 || n_segments >= (1LL << 30))
+    return fail(E3GNN_ERR_ARG, "segment sum: the number of segments must be in [1, 2^30)");
+  if (n_rows < 0 || n_rows > (1LL << 30)) return fail(E3GNN_ERR_ARG, "segment sum: row count out of range");
+  if (width != 1 && width != 6) return fail(E3GNN_ERR_ARG, "segment sum: width must be 1 or 6");
+  if (!ptr || !out || (n_rows > 0 && !in)) return fail(E3GNN_ERR_ARG, "segment sum: null array");
+  HIPCHK(launch_segment_sum((int)n_segments, ptr, (int)n_rows, width, in, out, (hipStream_t)stream));
+  return E3GNN_OK;
+}
+
+int e3gnn_energy_forces_batch(e3gnn_ctx* c, int64_t n_atoms, int64_t n_edges, int64_t B,
+                              const int32_t* atom_ptr, const int32_t* type,
+                              const int32_t* edge_center, const int32_t* edge_nbr,
+                              const float* edge_vec, float* energy, float* atomic_energy,
+                              float* forces, float* virial6, float* edge_grad, void* stream) {
+  if (!c) return fail(E3GNN_ERR_ARG, "null context");
+  if (B < 1 || B >= (1LL << 30))
+    return fail(E3GNN_ERR_ARG, "batch: the number of structures must be in [1, 2^30)");
+  if (B > n_atoms) return fail(E3GNN_ERR_ARG, "batch: more structures than atoms");
+  if (!atom_ptr) return fail(E3GNN_ERR_ARG, "batch: null atom_ptr");
+  if (!energy) return fail(E3GNN_ERR_ARG, "energy output is required");
+  // the evaluation of e3gnn_energy_forces on the concatenated graph ...
+  int rc = e3gnn_graph_set(c, n_atoms, 0, n_edges, type, edge_center, edge_nbr, edge_vec, stream);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  float* eat = atomic_energy;
+  if (!eat) {
+    HIPCHK(c->beat.ensure((size_t)n_atoms * sizeof(float)));
+    eat = c->beat.f();
+  }
+  if (virial6) HIPCHK(c->bw.ensure((size_t)n_atoms * 6 * sizeof(float)));
+  const int L = c->m->nlayer;
+  for (int t = 0; t < L; ++t)
+    if ((rc = e3gnn_layer_forward(c, t, stream))) return rc;
+  if ((rc = e3gnn_readout(c, nullptr, eat, stream))) return rc;
+  for (int t = L - 1; t >= 0; --t)
+    if ((rc = e3gnn_layer_backward(c, t, stream))) return rc;
+  if ((rc = e3gnn_forces(c, forces, nullptr, edge_grad, stream))) return rc;
+  // ... then the per-structure sums in a fixed order (segment_sum.hip): the
+  // energies from the atomic energies, the virials from the per-atom virials
+  // (both atoms of every edge lie in one structure, so its rows sum to its virial)
+  HIPCHK(launch_segment_sum((int)B, atom_ptr, (int)n_atoms, 1, eat, energy, s));
+  if (virial6) {
+    if ((rc = e3gnn_atom_virial(c, c->bw.f(), stream))) return rc;
+    HIPCHK(launch_segment_sum((int)B, atom_ptr, (int)n_atoms, 6, c->bw.f(), virial6, s));
+  }
+  if (!c->stream_ordered) {
+    HIPCHK(hipStreamSynchronize(s));
+  } else {
+    if (!c->done_ev) HIPCHK(hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(c->done_ev, s));
+    c->done_stream = s;
+    c->done_pending = true;
+  }
+  return E3GNN_OK;
+}
+
 int e3gnn_halo_pack(const int32_t* idx, int64_t n, int dim, const float* src, int64_t src_stride,
                     float* dst, void* stream) {
   if (n < 0 || dim <= 0) return fail(E3GNN_ERR_ARG, "bad halo size");
@@ -1122,7 +1184,7 @@ int64_t e3gnn_workspace_bytes(const e3gnn_ctx* c) {
   const DBuf* fixed[] = {&c->type, &c->center, &c->nbr, &c->vec, &c->row_ptr, &c->src_ptr,
                          &c->src_perm, &c->cnt, &c->err, &c->Y, &c->emb, &c->dY, &c->dgu, &c->demb,
                          &c->fe, &c->H1, &c->H2, &c->agg, &c->dw, &c->dxc, &c->dy, &c->dh,
-                         &c->eat, &c->part, &c->vpart, &c->scratch6};
+                         &c->eat, &c->part, &c->vpart, &c->scratch6, &c->beat, &c->bw};
   for (auto* d : fixed) b += (int64_t)d->cap;
   for (auto* v : {&c->x, &c->grad, &c->h, &c->y, &c->w, &c->a1, &c->a2})
     for (auto& d : *v) b += (int64_t)d.cap;

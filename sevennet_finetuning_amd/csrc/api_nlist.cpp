@@ -1,5 +1,5 @@
-// The device neighbour list and rank graph behind the C ABI (include/e3gnn.h;
-// kernels in neighbor.hip).
+// The device neighbour list, its batched form and the rank graph behind the C
+// ABI (include/e3gnn.h; kernels in neighbor.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +31,12 @@ struct e3gnn_nlist {
   int world = 0;
   DBuf flag, fpos, centers, bflag, degrow, owned, gid, ghosts, lid, hist, hoff, recv, sc_sum,
       sc_off;
+  // batch (e3gnn_nlist_batch_build): B structures, their geometries and row ranges
+  bool batch_built = false;
+  int64_t B = 0;
+  DBuf geoms, batch, aptr;
+  std::vector<NlGeomB> hgeoms;  // host images of the uploads: alive until the next build
+  std::vector<int32_t> haptr;
 };
 
 e3gnn_nlist* e3gnn_nlist_create(int device) {
@@ -57,6 +63,55 @@ void nl_bins(NlGeom& G, const double h[3], double rc, int64_t n) {
   for (int k = 0; k < 3; ++k) G.R[k] = std::max(1, (int)std::ceil(rc * G.nb[k] / h[k]));
 }
 
+// Periodic cell (rows a, b, c): G.cell, G.inv and the heights.  Returns the
+// refusal or nullptr.
+const char* nl_cell_geom(NlGeom& G, const double* cell, double hgt[3]) {
+  for (int k = 0; k < 9; ++k) G.cell[k] = cell[k];
+  const double* a = cell;
+  const double det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) +
+                     a[2] * (a[3] * a[7] - a[4] * a[6]);
+  if (!(std::fabs(det) > 1e-12)) return "singular cell";
+  // inverse (rows of cell = lattice vectors): frac = pos @ inv
+  G.inv[0] = (a[4] * a[8] - a[5] * a[7]) / det;
+  G.inv[1] = (a[2] * a[7] - a[1] * a[8]) / det;
+  G.inv[2] = (a[1] * a[5] - a[2] * a[4]) / det;
+  G.inv[3] = (a[5] * a[6] - a[3] * a[8]) / det;
+  G.inv[4] = (a[0] * a[8] - a[2] * a[6]) / det;
+  G.inv[5] = (a[2] * a[3] - a[0] * a[5]) / det;
+  G.inv[6] = (a[3] * a[7] - a[4] * a[6]) / det;
+  G.inv[7] = (a[1] * a[6] - a[0] * a[7]) / det;
+  G.inv[8] = (a[0] * a[4] - a[1] * a[3]) / det;
+  for (int k = 0; k < 3; ++k) {  // height along k = |det| / |a_{k+1} x a_{k+2}|
+    const double* u = a + 3 * ((k + 1) % 3);
+    const double* v = a + 3 * ((k + 2) % 3);
+    const double cx = u[1] * v[2] - u[2] * v[1], cy = u[2] * v[0] - u[0] * v[2],
+                 cz = u[0] * v[1] - u[1] * v[0];
+    hgt[k] = std::fabs(det) / std::sqrt(cx * cx + cy * cy + cz * cz);
+  }
+  return nullptr;
+}
+
+// Isolated cluster (hp: its n positions on the host): a virtual orthorhombic
+// box 1 A beyond the atoms on every side, so no image is ever within the
+// cutoff (S = 0 throughout).  Returns the refusal or nullptr.
+const char* nl_cluster_geom(NlGeom& G, const double* hp, int64_t n, double hgt[3]) {
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  for (int64_t a = 0; a < n; ++a)
+    for (int k = 0; k < 3; ++k) {
+      const double v = hp[3 * a + k];
+      if (!std::isfinite(v)) return "non-finite position";
+      lo[k] = a ? std::min(lo[k], v) : v;
+      hi[k] = a ? std::max(hi[k], v) : v;
+    }
+  for (int k = 0; k < 3; ++k) {
+    G.origin[k] = lo[k] - 1.0;
+    hgt[k] = (hi[k] - lo[k]) + 2.0;
+    G.cell[4 * k] = hgt[k];
+    G.inv[4 * k] = 1.0 / hgt[k];
+  }
+  return nullptr;
+}
+
 // The geometry of the box and the atoms binned (k_nl_bin, scan, k_nl_place):
 // the part e3gnn_nlist_build and e3gnn_nlist_rank_build share.  `all`: all
 // three dimensions periodic, else an isolated cluster.
@@ -65,6 +120,7 @@ int nl_bin_atoms(e3gnn_nlist* h, int64_t n, const double* pos, const double* cel
   HIPCHK(hipSetDevice(h->device));
   h->built = false;
   h->rank_built = false;
+  h->batch_built = false;
   h->n = n;
   h->pos = pos;
   NlGeom& G = h->G;
@@ -74,47 +130,11 @@ int nl_bin_atoms(e3gnn_nlist* h, int64_t n, const double* pos, const double* cel
   double hgt[3];
   if (all) {
     if (!cell) return fail(E3GNN_ERR_ARG, "null cell");
-    for (int k = 0; k < 9; ++k) G.cell[k] = cell[k];
-    const double* a = cell;
-    const double det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) +
-                       a[2] * (a[3] * a[7] - a[4] * a[6]);
-    if (!(std::fabs(det) > 1e-12)) return fail(E3GNN_ERR_ARG, "singular cell");
-    // inverse (rows of cell = lattice vectors): frac = pos @ inv
-    G.inv[0] = (a[4] * a[8] - a[5] * a[7]) / det;
-    G.inv[1] = (a[2] * a[7] - a[1] * a[8]) / det;
-    G.inv[2] = (a[1] * a[5] - a[2] * a[4]) / det;
-    G.inv[3] = (a[5] * a[6] - a[3] * a[8]) / det;
-    G.inv[4] = (a[0] * a[8] - a[2] * a[6]) / det;
-    G.inv[5] = (a[2] * a[3] - a[0] * a[5]) / det;
-    G.inv[6] = (a[3] * a[7] - a[4] * a[6]) / det;
-    G.inv[7] = (a[1] * a[6] - a[0] * a[7]) / det;
-    G.inv[8] = (a[0] * a[4] - a[1] * a[3]) / det;
-    for (int k = 0; k < 3; ++k) {  // height along k = |det| / |a_{k+1} x a_{k+2}|
-      const double* u = a + 3 * ((k + 1) % 3);
-      const double* v = a + 3 * ((k + 2) % 3);
-      const double cx = u[1] * v[2] - u[2] * v[1], cy = u[2] * v[0] - u[0] * v[2],
-                   cz = u[0] * v[1] - u[1] * v[0];
-      hgt[k] = std::fabs(det) / std::sqrt(cx * cx + cy * cy + cz * cz);
-    }
+    if (const char* why = nl_cell_geom(G, cell, hgt)) return fail(E3GNN_ERR_ARG, why);
   } else {
-    // isolated cluster: a virtual orthorhombic box 1 A beyond the atoms on
-    // every side, so no image is ever within the cutoff (S = 0 throughout)
     std::vector<double> hp((size_t)n * 3);
     if (n) HIPCHK(hipMemcpy(hp.data(), pos, hp.size() * 8, hipMemcpyDefault));
-    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    for (int64_t a = 0; a < n; ++a)
-      for (int k = 0; k < 3; ++k) {
-        const double v = hp[3 * a + k];
-        if (!std::isfinite(v)) return fail(E3GNN_ERR_ARG, "non-finite position");
-        lo[k] = a ? std::min(lo[k], v) : v;
-        hi[k] = a ? std::max(hi[k], v) : v;
-      }
-    for (int k = 0; k < 3; ++k) {
-      G.origin[k] = lo[k] - 1.0;
-      hgt[k] = (hi[k] - lo[k]) + 2.0;
-      G.cell[4 * k] = hgt[k];
-      G.inv[4 * k] = 1.0 / hgt[k];
-    }
+    if (const char* why = nl_cluster_geom(G, hp.data(), n, hgt)) return fail(E3GNN_ERR_ARG, why);
   }
   nl_bins(G, hgt, cutoff, n);
   const int nbins = G.nb[0] * G.nb[1] * G.nb[2];
@@ -326,6 +346,142 @@ int e3gnn_nlist_rank_fetch(e3gnn_nlist* h, int32_t* owned, int32_t* ghosts, int6
   HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (herr & 2) return fail(E3GNN_ERR_GRAPH, "periodic image shift beyond +-1024 cells");
+  return E3GNN_OK;
+}
+
+// ------------------------------------------------------------------- batch
+namespace {
+// Argument rules of e3gnn_nlist_batch_build, checked before any device work
+// (host only: no handle state, no HIP call).  Returns the refusal or "".
+std::string nl_batch_args(bool have_handle, int64_t B, const int64_t* atom_ptr, const double* pos,
+                          const double* cells, const int32_t* periodic, double cutoff) {
+  if (B < 1 || B >= (int64_t)1 << 30) return "batch: the number of structures must be in [1, 2^30)";
+  if (!atom_ptr) return "batch: null atom_ptr";
+  if (!(cutoff > 0)) return "cutoff must be positive";
+  if (!periodic) return "batch: null periodic flags";
+  if (atom_ptr[0] != 0) return "batch: atom_ptr[0] must be 0";
+  for (int64_t s = 0; s < B; ++s) {
+    if (atom_ptr[s + 1] <= atom_ptr[s])
+      return "batch: structure " + std::to_string(s) +
+             " is empty or atom_ptr decreases (every structure needs at least one atom)";
+    if (atom_ptr[s + 1] >= (int64_t)1 << 30) return "batch: atom count out of range (2^30)";
+    if (periodic[s] != 0 && periodic[s] != 7)
+      return "batch: structure " + std::to_string(s) +
+             ": device neighbour list: pbc must be all true or all false";
+    if (periodic[s] && !cells) return "batch: null cells";
+  }
+  if (!pos) return "null positions";
+  if (!have_handle) return "null neighbour-list handle";
+  return "";
+}
+}  // namespace
+
+int e3gnn_nlist_batch_build(e3gnn_nlist* h, int64_t B, const int64_t* atom_ptr, const double* pos,
+                            const double* cells, const int32_t* periodic, double cutoff,
+                            int64_t* n_edges, void* stream) {
+  {
+    const std::string why = nl_batch_args(h != nullptr, B, atom_ptr, pos, cells, periodic, cutoff);
+    if (!why.empty()) return fail(E3GNN_ERR_ARG, why);
+  }
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  h->built = false;
+  h->rank_built = false;
+  h->batch_built = false;
+  const int64_t n = atom_ptr[B];
+  h->n = n;
+  h->B = B;
+  h->pos = pos;
+  // the geometries, as nl_bin_atoms computes the one of a single structure;
+  // isolated members need their extent: one copy of the positions per batch
+  std::vector<double> hp;
+  bool any_isolated = false;
+  for (int64_t k = 0; k < B; ++k) any_isolated |= periodic[k] == 0;
+  if (any_isolated) {
+    hp.resize((size_t)n * 3);
+    HIPCHK(hipMemcpy(hp.data(), pos, hp.size() * 8, hipMemcpyDefault));
+  }
+  h->hgeoms.assign((size_t)B, NlGeomB{});
+  h->haptr.resize((size_t)B + 1);
+  int64_t nbins = 0;
+  for (int64_t k = 0; k < B; ++k) {
+    NlGeom& G = h->hgeoms[k].G;
+    const int64_t n_k = atom_ptr[k + 1] - atom_ptr[k];
+    G.rc2 = cutoff * cutoff;
+    G.periodic = periodic[k] ? 1 : 0;
+    double hgt[3];
+    const char* why = periodic[k] ? nl_cell_geom(G, cells + 9 * k, hgt)
+                                  : nl_cluster_geom(G, hp.data() + 3 * atom_ptr[k], n_k, hgt);
+    if (why) return fail(E3GNN_ERR_ARG, "batch: structure " + std::to_string(k) + ": " + why);
+    nl_bins(G, hgt, cutoff, n_k);
+    h->hgeoms[k].bin_base = (int)nbins;
+    h->haptr[k] = (int32_t)atom_ptr[k];
+    nbins += (int64_t)G.nb[0] * G.nb[1] * G.nb[2];
+    if (nbins >= (int64_t)1 << 31) return fail(E3GNN_ERR_ARG, "batch: bin count exceeds int32");
+  }
+  h->haptr[B] = (int32_t)n;
+  if (h->f0.ensure((size_t)n * 12) != hipSuccess || h->bin.ensure((size_t)n * 4) != hipSuccess ||
+      h->bin_atoms.ensure((size_t)n * 4) != hipSuccess || h->deg.ensure((size_t)n * 4) != hipSuccess ||
+      h->row_ptr.ensure((size_t)(n + 1) * 4) != hipSuccess ||
+      h->bin_count.ensure((size_t)nbins * 4) != hipSuccess ||
+      h->bin_start.ensure((size_t)(nbins + 1) * 4) != hipSuccess ||
+      h->cursor.ensure((size_t)nbins * 4) != hipSuccess || h->err.ensure(16) != hipSuccess ||
+      h->geoms.ensure((size_t)B * sizeof(NlGeomB)) != hipSuccess ||
+      h->batch.ensure((size_t)n * 4) != hipSuccess || h->aptr.ensure((size_t)(B + 1) * 4) != hipSuccess)
+    return fail(E3GNN_ERR_HIP, "neighbour-list workspace allocation failed");
+  int* err = h->err.i();
+  const NlGeomB* geoms = (const NlGeomB*)h->geoms.p;
+  HIPCHK(hipMemcpyAsync(h->geoms.p, h->hgeoms.data(), (size_t)B * sizeof(NlGeomB),
+                        hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->aptr.p, h->haptr.data(), (size_t)(B + 1) * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(err, 0, 16, s));
+  HIPCHK(hipMemsetAsync(h->bin_count.p, 0, (size_t)nbins * 4, s));
+  HIPCHK(hipMemsetAsync(h->cursor.p, 0, (size_t)nbins * 4, s));
+  HIPCHK(launch_nlb_batch((int)B, h->aptr.i(), h->batch.i(), s));
+  HIPCHK(launch_nlb_bin((int)n, pos, geoms, h->batch.i(), h->f0.i(), h->bin.i(), h->bin_count.i(),
+                        err, s));
+  HIPCHK(launch_nl_scan((int)nbins, h->bin_count.i(), h->bin_start.i(), s));
+  HIPCHK(launch_nl_place((int)n, h->bin.i(), h->bin_start.i(), h->cursor.i(), h->bin_atoms.i(), s));
+  HIPCHK(launch_nlb_search(false, (int)n, pos, geoms, h->batch.i(), h->f0.i(), h->bin.i(),
+                           h->bin_start.i(), h->bin_atoms.i(), h->deg.i(), nullptr, nullptr, nullptr,
+                           nullptr, nullptr, err, s));
+  HIPCHK(launch_nl_scan((int)n, h->deg.i(), h->row_ptr.i(), s));
+  int herr[4] = {0, 0, 0, 0}, total = 0;
+  HIPCHK(hipMemcpyAsync(herr, err, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&total, h->row_ptr.i() + n, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (herr[0] & 1)
+    return fail(E3GNN_ERR_ARG, "batch: structure " + std::to_string(herr[1] - 1) +
+                                   ": non-finite or out-of-box atom position");
+  if (herr[0] & 4)
+    return fail(E3GNN_ERR_GRAPH, "batch: structure " + std::to_string(herr[3] - 1) +
+                                     ": a centre has more than " + std::to_string(NL_MAXD) +
+                                     " neighbours (device neighbour-list limit)");
+  if (total < 0) return fail(E3GNN_ERR_GRAPH, "edge count exceeds int32");
+  h->E = total;
+  h->batch_built = true;
+  if (n_edges) *n_edges = total;
+  return E3GNN_OK;
+}
+
+int e3gnn_nlist_batch_fetch(e3gnn_nlist* h, int32_t* edge_center, int32_t* edge_nbr, int32_t* shift,
+                            float* edge_vec, int64_t* edge_ptr, void* stream) {
+  if (!h || !h->batch_built) return fail(E3GNN_ERR_ARG, "batched neighbour list not built");
+  if (h->E > 0 && (!edge_center || !edge_nbr)) return fail(E3GNN_ERR_ARG, "null edge output");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  int* err = h->err.i();
+  HIPCHK(hipMemsetAsync(err, 0, 16, s));
+  HIPCHK(launch_nlb_search(true, (int)h->n, h->pos, (const NlGeomB*)h->geoms.p, h->batch.i(),
+                           h->f0.i(), h->bin.i(), h->bin_start.i(), h->bin_atoms.i(), nullptr,
+                           h->row_ptr.i(), edge_center, edge_nbr, shift, edge_vec, err, s));
+  if (edge_ptr) HIPCHK(launch_nlb_edge_ptr((int)h->B, h->aptr.i(), h->row_ptr.i(), edge_ptr, s));
+  int herr[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(herr, err, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (herr[0] & 2)
+    return fail(E3GNN_ERR_GRAPH, "batch: structure " + std::to_string(herr[2] - 1) +
+                                     ": periodic image shift beyond +-1024 cells");
   return E3GNN_OK;
 }
 

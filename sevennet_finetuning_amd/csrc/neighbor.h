@@ -64,4 +64,26 @@ hipError_t launch_rk_ghost_sort(bool scatter, int ng, int world, int nblk, const
 hipError_t launch_rk_recv(int world, int nblk, const int* off, int64_t* recv_counts,
                           hipStream_t s);
 
+// Batched form (B structures concatenated, one set of launches): structure s
+// owns the rows [atom_ptr[s], atom_ptr[s+1]) and the bins [bin_base, bin_base +
+// nb[0] nb[1] nb[2]) of one concatenated bin array, so candidates never cross
+// structures.  err is int[4]: the flags of the single build (1, 2, 4) and, for
+// each, 1 + the largest offending structure index (err[1], err[2], err[3]).
+struct NlGeomB {
+  NlGeom G;
+  int bin_base;
+};
+// batch[a] = s for a in [atom_ptr[s], atom_ptr[s+1])
+hipError_t launch_nlb_batch(int B, const int* atom_ptr, int* batch, hipStream_t s);
+hipError_t launch_nlb_bin(int n, const double* pos, const NlGeomB* geoms, const int* batch, int* f0,
+                          int* bin, int* bin_count, int* err, hipStream_t s);
+hipError_t launch_nlb_search(bool fill, int n, const double* pos, const NlGeomB* geoms,
+                             const int* batch, const int* f0, const int* bin,
+                             const int* bin_start, const int* bin_atoms, int* deg,
+                             const int* row_ptr, int* center, int* nbr, int* shift, float* vec,
+                             int* err, hipStream_t s);
+// edge_ptr[s] = row_ptr[atom_ptr[s]], s in [0, B]
+hipError_t launch_nlb_edge_ptr(int B, const int* atom_ptr, const int* row_ptr, int64_t* edge_ptr,
+                               hipStream_t s);
+
 }  // namespace e3gnn

@@ -17,6 +17,9 @@
 // Pass 1 counts each centre's edges (one wave per centre, ballot), a scan gives
 // the CSR offsets, pass 2 recomputes the hits into LDS, sorts the centre's keys
 // (j, Sx, Sy, Sz) with a bitonic network and writes them: deterministic.
+//
+// The batched form (k_nlb_*, at the end) runs the same passes over many
+// structures concatenated, each with its own geometry and bins.
 #include "neighbor.h"
 
 #pragma clang fp contract(off)
@@ -375,6 +378,186 @@ __global__ void k_rk_recv(int world, int nblk, const int* __restrict__ off,
   recv_counts[o] = (long long)off[(o + 1) * nblk] - off[o * nblk];
 }
 
+// ---------------------------------------------------------------- batch
+// B structures concatenated: the passes of the single build over all rows at
+// once.  A thread (k_nlb_bin) or a wave (k_nlb_search) reads its structure's
+// geometry from geoms[batch[row]]; bins are numbered through the whole batch
+// (NlGeomB::bin_base), so the bin arrays, k_nl_place and both scans serve as
+// they are, and a centre only ever meets atoms of its own structure.  The
+// inclusion test is nl_vec / r2 above, unchanged.
+
+__global__ void k_nlb_batch(const int* __restrict__ atom_ptr, int* __restrict__ batch) {
+  const int s = blockIdx.x;
+  for (int a = atom_ptr[s] + threadIdx.x; a < atom_ptr[s + 1]; a += blockDim.x) batch[a] = s;
+}
+
+__device__ __forceinline__ void nlb_flag(int* __restrict__ err, int bit, int slot, int s) {
+  atomicOr(err, bit);
+  atomicMax(err + slot, s + 1);
+}
+
+__global__ void k_nlb_bin(int n, const double* __restrict__ pos,
+                          const NlGeomB* __restrict__ geoms, const int* __restrict__ batch,
+                          int* __restrict__ f0, int* __restrict__ bin,
+                          int* __restrict__ bin_count, int* __restrict__ err) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= n) return;
+  const int st = batch[a];
+  const NlGeom& G = geoms[st].G;
+  const double p0 = pos[3 * a] - G.origin[0], p1 = pos[3 * a + 1] - G.origin[1],
+               p2 = pos[3 * a + 2] - G.origin[2];
+  int b[3], fl3[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double f = ((p0 * G.inv[k]) + (p1 * G.inv[3 + k])) + (p2 * G.inv[6 + k]);
+    const double fl = floor(f);
+    const double fw = f - fl;
+    int bk = (int)(fw * G.nb[k]);
+    bk = bk < 0 ? 0 : (bk >= G.nb[k] ? G.nb[k] - 1 : bk);
+    b[k] = bk;
+    if (!(fl > -1e9 && fl < 1e9)) nlb_flag(err, 1, 1, st);  // non-finite or absurd position
+    fl3[k] = (int)fl;
+    f0[3 * a + k] = fl3[k];
+  }
+  if (!G.periodic && (fl3[0] | fl3[1] | fl3[2])) nlb_flag(err, 1, 1, st);
+  const int id = geoms[st].bin_base + ((b[0] * G.nb[1] + b[1]) * G.nb[2] + b[2]);
+  bin[a] = id;
+  atomicAdd(&bin_count[id], 1);
+}
+
+// k_nl_search<FILL, false> with the geometry per structure; rows, bins and keys
+// are those of the concatenated batch, so a structure's edges come out in the
+// single build's order with its first row added to i and j
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_nlb_search(
+    int n, const double* __restrict__ pos, const NlGeomB* __restrict__ geoms,
+    const int* __restrict__ batch, const int* __restrict__ f0, const int* __restrict__ bin,
+    const int* __restrict__ bin_start, const int* __restrict__ bin_atoms, int* __restrict__ deg,
+    const int* __restrict__ row_ptr, int* __restrict__ center, int* __restrict__ nbr,
+    int* __restrict__ shift, float* __restrict__ vec, int* __restrict__ err) {
+  __shared__ unsigned long long keys[4][NL_MAXD];
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wid);
+  if (i >= n) return;
+  const int st = __builtin_amdgcn_readfirstlane(batch[i]);
+  const NlGeom& G = geoms[st].G;  // wave-uniform address
+  const int bin_base = geoms[st].bin_base;
+  const int nb[3] = {G.nb[0], G.nb[1], G.nb[2]};
+  const int R[3] = {G.R[0], G.R[1], G.R[2]};
+  const int periodic = G.periodic;
+  unsigned long long* K = keys[wid];
+  const int bi = bin[i] - bin_base;
+  const int b[3] = {bi / (nb[1] * nb[2]), (bi / nb[2]) % nb[1], bi % nb[2]};
+  const int fi[3] = {f0[3 * i], f0[3 * i + 1], f0[3 * i + 2]};
+  const double rc2 = G.rc2;
+  int count = 0;  // uniform
+  for (int ox = -R[0]; ox <= R[0]; ++ox)
+    for (int oy = -R[1]; oy <= R[1]; ++oy)
+      for (int oz = -R[2]; oz <= R[2]; ++oz) {
+        const int o[3] = {ox, oy, oz};
+        int c[3], sh[3];
+        bool skip = false;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const int v = b[k] + o[k];
+          if (periodic) {
+            sh[k] = v >= 0 ? v / nb[k] : -((-v + nb[k] - 1) / nb[k]);
+            c[k] = v - sh[k] * nb[k];
+          } else {
+            sh[k] = 0;
+            c[k] = v;
+            skip |= v < 0 || v >= nb[k];
+          }
+        }
+        if (skip) continue;
+        const int id = bin_base + ((c[0] * nb[1] + c[1]) * nb[2] + c[2]);
+        const int s = bin_start[id], e = bin_start[id + 1];
+        for (int t0 = s; t0 < e; t0 += 64) {
+          const int t = t0 + lane;
+          bool hit = false;
+          int j = 0, S[3] = {0, 0, 0};
+          if (t < e) {
+            j = bin_atoms[t];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) S[k] = sh[k] + fi[k] - f0[3 * j + k];
+            const Hit h = nl_vec(pos, G, i, j, S[0], S[1], S[2]);
+            const double r2 = ((h.d[0] * h.d[0]) + (h.d[1] * h.d[1])) + (h.d[2] * h.d[2]);
+            hit = r2 < rc2 && !(j == i && S[0] == 0 && S[1] == 0 && S[2] == 0);
+          }
+          const unsigned long long m = __ballot(hit);
+          if (FILL && hit) {
+            const int slot = count + __popcll(m & ((1ull << lane) - 1));
+            const int lim = 1 << SB;
+            if (S[0] < -lim || S[0] >= lim || S[1] < -lim || S[1] >= lim || S[2] < -lim ||
+                S[2] >= lim)
+              nlb_flag(err, 2, 2, st);
+            else if (slot < NL_MAXD)
+              K[slot] = nl_key(j, S[0], S[1], S[2]);
+          }
+          count += __popcll(m);
+        }
+      }
+  if constexpr (!FILL) {
+    if (lane == 0) {
+      deg[i] = count;
+      if (count > NL_MAXD) nlb_flag(err, 4, 3, st);
+    }
+    return;
+  } else {
+    if (count > NL_MAXD) return;  // reported by the count pass
+    // bitonic sort of K[0..P) (P = next power of two; padding = max key)
+    int P = 1;
+    while (P < count) P <<= 1;
+    for (int t = count + lane; t < P; t += 64) K[t] = ~0ull;
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    for (int k = 2; k <= P; k <<= 1)
+      for (int jj = k >> 1; jj > 0; jj >>= 1) {
+        for (int t = lane; t < P; t += 64) {
+          const int u = t ^ jj;
+          if (u > t) {
+            const unsigned long long a = K[t], c = K[u];
+            const bool up = (t & k) == 0;
+            if ((a > c) == up) {
+              K[t] = c;
+              K[u] = a;
+            }
+          }
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      }
+    const int base = row_ptr[i];
+    for (int t = lane; t < count; t += 64) {
+      const unsigned long long key = K[t];
+      const int j = (int)(key >> 33);
+      const int sx = (int)((key >> 22) & 0x7ff) - (1 << SB);
+      const int sy = (int)((key >> 11) & 0x7ff) - (1 << SB);
+      const int sz = (int)(key & 0x7ff) - (1 << SB);
+      const Hit h = nl_vec(pos, G, i, j, sx, sy, sz);
+      const int64_t q = (int64_t)base + t;
+      center[q] = i;
+      nbr[q] = j;
+      if (shift) {
+        shift[3 * q] = sx;
+        shift[3 * q + 1] = sy;
+        shift[3 * q + 2] = sz;
+      }
+      if (vec) {
+        vec[3 * q] = (float)h.d[0];
+        vec[3 * q + 1] = (float)h.d[1];
+        vec[3 * q + 2] = (float)h.d[2];
+      }
+    }
+  }
+}
+
+__global__ void k_nlb_edge_ptr(int B, const int* __restrict__ atom_ptr,
+                               const int* __restrict__ row_ptr, long long* __restrict__ edge_ptr) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s <= B) edge_ptr[s] = row_ptr[atom_ptr[s]];
+}
+
 }  // namespace
 
 hipError_t launch_nl_bin(int n, const double* pos, const NlGeom& G, int* f0, int* bin,
@@ -469,6 +652,40 @@ hipError_t launch_rk_recv(int world, int nblk, const int* off, int64_t* recv_cou
                           hipStream_t s) {
   hipLaunchKernelGGL(k_rk_recv, dim3((world + 63) / 64), dim3(64), 0, s, world, nblk, off,
                      (long long*)recv_counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_nlb_batch(int B, const int* atom_ptr, int* batch, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_nlb_batch, dim3(B), dim3(256), 0, s, atom_ptr, batch);
+  return hipGetLastError();
+}
+hipError_t launch_nlb_bin(int n, const double* pos, const NlGeomB* geoms, const int* batch, int* f0,
+                          int* bin, int* bin_count, int* err, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_nlb_bin, dim3((n + 255) / 256), dim3(256), 0, s, n, pos, geoms, batch, f0,
+                     bin, bin_count, err);
+  return hipGetLastError();
+}
+hipError_t launch_nlb_search(bool fill, int n, const double* pos, const NlGeomB* geoms,
+                             const int* batch, const int* f0, const int* bin,
+                             const int* bin_start, const int* bin_atoms, int* deg,
+                             const int* row_ptr, int* center, int* nbr, int* shift, float* vec,
+                             int* err, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const dim3 grid((n + 3) / 4), block(256);
+  if (fill)
+    hipLaunchKernelGGL(k_nlb_search<true>, grid, block, 0, s, n, pos, geoms, batch, f0, bin,
+                       bin_start, bin_atoms, deg, row_ptr, center, nbr, shift, vec, err);
+  else
+    hipLaunchKernelGGL(k_nlb_search<false>, grid, block, 0, s, n, pos, geoms, batch, f0, bin,
+                       bin_start, bin_atoms, deg, row_ptr, center, nbr, shift, vec, err);
+  return hipGetLastError();
+}
+hipError_t launch_nlb_edge_ptr(int B, const int* atom_ptr, const int* row_ptr, int64_t* edge_ptr,
+                               hipStream_t s) {
+  hipLaunchKernelGGL(k_nlb_edge_ptr, dim3((B + 1 + 255) / 256), dim3(256), 0, s, B, atom_ptr,
+                     row_ptr, (long long*)edge_ptr);
   return hipGetLastError();
 }
 

@@ -47,6 +47,27 @@ def atom_virial_partition(n, edge_center, edge_nbr, edge_vec, edge_grad):
     return w
 
 
+def segment_sum(rows, ptr):
+    """``out[s] = rows[ptr[s]:ptr[s + 1]].sum(0)`` for device tensors ``rows``
+    (float32 [n] or [n, 6]) and ``ptr`` (int32 [B + 1]), in the fixed order of
+    e3gnn_segment_sum (csrc/segment_sum.hip) -- the per-structure sums of
+    ``E3GNNModel.energy_forces_batch``.  No atomics: two calls give equal bits."""
+    lib = _lib.load()
+    dev = rows.device
+    if dev.type != 'cuda':
+        raise _lib.E3GNNError(f'the HIP path needs a GPU device, got {dev}')
+    rows = rows.to(torch.float32).contiguous()
+    ptr = ptr.to(dev, torch.int32).contiguous()
+    width = 1 if rows.dim() == 1 else int(rows.shape[1])
+    B = int(ptr.shape[0]) - 1
+    out = torch.empty((max(B, 0),) + tuple(rows.shape[1:]), device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.e3gnn_segment_sum(B, ptr.data_ptr(), int(rows.shape[0]), width,
+                                         rows.data_ptr(), out.data_ptr(),
+                                         torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
 class E3GNNModel:
     """A loaded deployment (weights.bin + manifest.json) on one HIP device."""
 
@@ -141,6 +162,39 @@ class E3GNNModel:
             w = torch.empty(n, 6, device=dev)
             _lib.check(self.lib.e3gnn_atom_virial(self._ctx, w.data_ptr(), self.stream_handle()))
             out['atomic_virial'] = w
+        return out
+
+    def energy_forces_batch(self, types, edge_center, edge_nbr, edge_vec, atom_ptr,
+                            want_virial=True):
+        """One evaluation of a batch of structures concatenated (the graph of
+        ``DeviceNeighborList.batch``; ``atom_ptr`` int32 [B + 1], structure s
+        owns the rows ``atom_ptr[s]:atom_ptr[s + 1]``, no edge joins two
+        structures).  Returns dict of device tensors: ``energy`` [B],
+        ``atomic_energy`` [n], ``forces`` [n, 3] and, with ``want_virial``,
+        ``virial`` [B, 6] (xx, yy, zz, xy, yz, zx).  The per-structure sums run
+        in a fixed order on the device (e3gnn_energy_forces_batch): two calls
+        give equal bits."""
+        dev = self.device
+        n = int(types.shape[0])
+        E = int(edge_center.shape[0])
+        B = int(atom_ptr.shape[0]) - 1
+        types = types.to(dev, torch.int32).contiguous()
+        edge_center = edge_center.to(dev, torch.int32).contiguous()
+        edge_nbr = edge_nbr.to(dev, torch.int32).contiguous()
+        edge_vec = edge_vec.to(dev, torch.float32).contiguous()
+        atom_ptr = atom_ptr.to(dev, torch.int32).contiguous()
+        energy = torch.empty(max(B, 0), device=dev)
+        eat = torch.empty(n, device=dev)
+        forces = torch.empty(n, 3, device=dev)
+        virial = torch.empty(max(B, 0), 6, device=dev) if want_virial else None
+        _lib.check(self.lib.e3gnn_energy_forces_batch(
+            self._ctx, n, E, B, atom_ptr.data_ptr(), types.data_ptr(), edge_center.data_ptr(),
+            edge_nbr.data_ptr(), edge_vec.data_ptr(), energy.data_ptr(), eat.data_ptr(),
+            forces.data_ptr(), virial.data_ptr() if virial is not None else None, None,
+            self.stream_handle()))
+        out = {'energy': energy, 'atomic_energy': eat, 'forces': forces}
+        if virial is not None:
+            out['virial'] = virial
         return out
 
     def set_impl(self, impl):

@@ -40,18 +40,24 @@ def _brute(pos, cell, cutoff, pbc, centers=None):
     h = _heights(cell) if any(pbc) else np.ones(3)
     ci = np.arange(len(pos)) if centers is None else np.asarray(centers, dtype=np.int64)
     reps = [int(np.ceil(cutoff / h[k])) if pbc[k] else 0 for k in range(3)]
+    # unwrapped coordinates (MD-style): the images are enumerated around the
+    # wrapped atoms, S = image + f0[i] - f0[j] as in _cell_list, and the test
+    # runs on the positions as given (f0 = 0 throughout for wrapped input)
+    f0 = np.zeros((len(pos), 3))
+    if any(pbc):
+        per = np.array([bool(p) for p in pbc])
+        f0[:, per] = np.floor(pos @ np.linalg.inv(cell))[:, per]
     ii, jj, ss = [], [], []
     for s in itertools.product(*[range(-r, r + 1) for r in reps]):
-        s = np.array(s, dtype=np.float64)
-        d = _rij(pos[None, :, :], pos[ci, None, :], s, cell)
+        S = np.array(s, dtype=np.float64) + f0[ci][:, None, :] - f0[None, :, :]
+        d = _rij(pos[None, :, :], pos[ci, None, :], S, cell)
         mask = _r2(d) < cutoff * cutoff
-        if not s.any():
+        if not any(s):
             mask[np.arange(len(ci)), ci] = False
         i, j = np.nonzero(mask)
-        i = ci[i]
-        ii.append(i)
+        ii.append(ci[i])
         jj.append(j)
-        ss.append(np.broadcast_to(s, (len(i), 3)))
+        ss.append(S[i, j])
     return np.concatenate(ii), np.concatenate(jj), np.concatenate(ss)
 
 
@@ -109,6 +115,27 @@ def neighbor_list(pos, cell, cutoff, pbc=(True, True, True), centers=None):
             np.ascontiguousarray(s[order]))
 
 
+def batch_neighbor_list(structs, cutoff):
+    """The graph of a batch of structures: every structure's ``neighbor_list``
+    with its first row added to i and j, one structure after the other -- the
+    contract of ``DeviceNeighborList.batch`` stated on the host.
+
+    ``structs``: sequence of ``(pos, cell, pbc)`` (``cell`` may be None for an
+    isolated structure).  Returns ``(edge_index int64 [2, E], shift float64
+    [E, 3], atom_ptr int64 [B + 1], edge_ptr int64 [B + 1])``."""
+    eis, shs, atom_ptr, edge_ptr = [], [], [0], [0]
+    for pos, cell, pbc in structs:
+        ei, sh = neighbor_list(pos, cell, cutoff, tuple(bool(p) for p in pbc))
+        eis.append(ei + atom_ptr[-1])
+        shs.append(sh)
+        atom_ptr.append(atom_ptr[-1] + len(pos))
+        edge_ptr.append(edge_ptr[-1] + ei.shape[1])
+    ei = np.concatenate(eis, axis=1) if eis else np.zeros((2, 0), dtype=np.int64)
+    sh = np.concatenate(shs) if shs else np.zeros((0, 3))
+    return (ei.astype(np.int64), np.ascontiguousarray(sh, dtype=np.float64),
+            np.array(atom_ptr, dtype=np.int64), np.array(edge_ptr, dtype=np.int64))
+
+
 class DeviceNeighborList:
     """Neighbour list on the GPU (libe3gnn_hip.so ``e3gnn_nlist_*``), the same
     edges, order and integer shifts as ``neighbor_list`` (bit for bit).
@@ -121,7 +148,11 @@ class DeviceNeighborList:
 
     ``rank_graph(pos, cell, cutoff, owner, rank, world)`` builds one rank's
     graph of a spatial decomposition on the same handle (see there and
-    ``parallel.build_rank_graph_device``)."""
+    ``parallel.build_rank_graph_device``).
+
+    ``batch(positions_list, cells_list, cutoff, pbc_list)`` builds the graphs of
+    many structures in one set of launches (``batch_neighbor_list`` on the
+    device)."""
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -160,6 +191,61 @@ class DeviceNeighborList:
         L.check(self.lib.e3gnn_nlist_fetch(self._h, center.data_ptr(), nbr.data_ptr(),
                                            shift.data_ptr(), vec.data_ptr(), s))
         return center, nbr, shift, vec
+
+    def batch(self, positions_list, cells_list, cutoff, pbc_list=None):
+        """The graphs of B structures in one build (``e3gnn_nlist_batch_*``):
+        ``batch_neighbor_list`` integer for integer.
+
+        ``positions_list``: B arrays [n_s, 3]; ``cells_list``: B cells (None
+        for an isolated structure); ``pbc_list``: B triples (default: all
+        periodic).  Returns device tensors ``(center int32 [E], nbr int32 [E],
+        shift int32 [E, 3], vec float32 [E, 3], atom_ptr int32 [B + 1],
+        edge_ptr int64 [B + 1])``; ``center`` / ``nbr`` are rows of the
+        concatenated batch.
+
+        Limits: every structure has at least one atom and is fully periodic
+        or fully isolated (anything else raises ``E3GNNError`` naming the
+        structure; ``neighbor_list`` covers those on the host), at most 512
+        neighbours per centre, shifts within +-1024 cells.  The outputs are
+        bitwise reproducible."""
+        import ctypes
+        torch, L = self._torch, self._L
+        dev = self.device
+        B = len(positions_list)
+        if pbc_list is None:
+            pbc_list = [(True, True, True)] * B
+        if len(cells_list) != B or len(pbc_list) != B:
+            raise ValueError('positions_list, cells_list and pbc_list must have one entry per '
+                             'structure')
+        pos = [np.asarray(p, dtype=np.float64).reshape(-1, 3) for p in positions_list]
+        atom_ptr = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum([len(p) for p in pos], out=atom_ptr[1:])
+        n = int(atom_ptr[-1])
+        cells = np.zeros((max(B, 1), 9), dtype=np.float64)
+        for k, c in enumerate(cells_list):
+            if c is not None:
+                cells[k] = np.asarray(c, dtype=np.float64).reshape(-1)
+        periodic = np.array([sum(int(bool(p)) << d for d, p in enumerate(pbc))
+                             for pbc in pbc_list], dtype=np.int32)
+        posd = torch.as_tensor(np.concatenate(pos) if B else np.zeros((0, 3))).to(dev).contiguous()
+        ne = ctypes.c_int64()
+        s = torch.cuda.current_stream(dev).cuda_stream
+        L.check(self.lib.e3gnn_nlist_batch_build(
+            self._h, B, atom_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), posd.data_ptr(),
+            cells.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+            periodic.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), float(cutoff),
+            ctypes.byref(ne), s))
+        E = ne.value
+        center = torch.empty(E, dtype=torch.int32, device=dev)
+        nbr = torch.empty(E, dtype=torch.int32, device=dev)
+        shift = torch.empty(E, 3, dtype=torch.int32, device=dev)
+        vec = torch.empty(E, 3, dtype=torch.float32, device=dev)
+        edge_ptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        L.check(self.lib.e3gnn_nlist_batch_fetch(self._h, center.data_ptr(), nbr.data_ptr(),
+                                                 shift.data_ptr(), vec.data_ptr(),
+                                                 edge_ptr.data_ptr(), s))
+        return (center, nbr, shift, vec,
+                torch.as_tensor(atom_ptr.astype(np.int32), device=dev), edge_ptr)
 
     def rank_graph(self, pos, cell, cutoff, owner, rank, world, pbc=(True, True, True)):
         """One rank's graph of a spatial decomposition, built on the device

@@ -47,6 +47,9 @@ class SevenNetCalculator(Calculator):
             raise ValueError('file_type should be checkpoint or torchscript')
         if not isinstance(device, (str, torch.device)):
             raise ValueError('device must be an instance of torch.device or str.')
+        loaded = model if hasattr(model, 'energy_forces') else None   # an engine of model.py
+        if loaded is not None:
+            device = loaded.device
         if isinstance(device, str) and device == 'auto':
             # the reference falls back to 'cpu' here (sevennet_calculator.py:57-62);
             # this build has no CPU engine, so 'auto' means the first GPU
@@ -60,10 +63,13 @@ class SevenNetCalculator(Calculator):
                 "model only on an AMD GPU through its HIP library (libe3gnn_hip.so); "
                 "there is no CPU path. Use device='cuda' / 'cuda:N' (ROCm) or 'auto'.")
         import os
-        path = model if os.path.isdir(str(model)) else pretrained_name_to_path(model)
-        # the native SevenNet-0 engine, or the generic one for other models of
-        # the family (e.g. the HfO2 example deployment)
-        self.model = load_model(path, device=self.device)
+        if loaded is not None:
+            self.model = loaded
+        else:
+            path = model if os.path.isdir(str(model)) else pretrained_name_to_path(model)
+            # the native SevenNet-0 engine, or the generic one for other models of
+            # the family (e.g. the HfO2 example deployment)
+            self.model = load_model(path, device=self.device)
         self.type_map = self.model.type_map()
         self.cutoff = self.model.cutoff
         self.sevennet_config = sevennet_config
@@ -135,6 +141,15 @@ class SevenNetCalculator(Calculator):
                 vec = torch.as_tensor(data[KEY.EDGE_VEC], dtype=torch.float32, device=g.device)
                 w = atom_virial_partition(len(atoms), ei[0], ei[1], vec, g).cpu().numpy()
                 self.results['stresses'] = -w[:, [0, 1, 2, 4, 5, 3]] / abs(data[KEY.CELL_VOLUME])
+
+
+    def calculate_many(self, atoms_list, max_atoms_per_batch=4096):
+        """Many structures, batched on the device (``inference.predict_many``):
+        one dict per structure, in input order, with ``energy``, ``energies``,
+        ``forces`` and, for periodic cells, ``stress`` as ``calculate`` gives
+        them."""
+        from .inference import predict_many
+        return predict_many(self, atoms_list, max_atoms_per_batch)
 
 
 class SevenNetD3Calculator(Calculator):
