@@ -589,6 +589,72 @@ int e3gnn_nlist_batch_build(e3gnn_nlist* h, int64_t B, const int64_t* atom_ptr, 
 int e3gnn_nlist_batch_fetch(e3gnn_nlist* h, int32_t* edge_center, int32_t* edge_nbr, int32_t* shift,
                             float* edge_vec, int64_t* edge_ptr, void* stream);
 
+/* ---- device-resident training dataset and batch assembly ----
+ * Replaces the host side of the reference's training input: the graph list of
+ * sevenn/train/dataload.py:71-140 held on the device, and PyG's Collater
+ * (sevenn/train/collate.py) as one gather launch per batch.
+ * e3gnn_dataset_create records DEVICE pointers to the concatenated dataset
+ * (the caller owns the arrays and keeps them alive) and copies the HOST
+ * atom_ptr / edge_ptr int64 [S+1] (both start at 0; every structure has at
+ * least one atom).  It makes no HIP call; NULL (with e3gnn_last_error) on a
+ * bad argument.  edge_center / edge_nbr are rows relative to the structure's
+ * first atom; shift may be NULL (batches then carry no pbc_shift). */
+typedef struct e3gnn_dataset e3gnn_dataset;
+typedef struct {
+  const int32_t* type;        /* [Na] */
+  const float* force;         /* [Na][3], NaN = unlabelled */
+  const int32_t* edge_center; /* [Ea] */
+  const int32_t* edge_nbr;    /* [Ea] */
+  const float* edge_vec;      /* [Ea][3] */
+  const float* shift;         /* [Ea][3] or NULL */
+  const float* energy;        /* [S] */
+  const float* stress;        /* [S][6] */
+  const float* volume;        /* [S] */
+} e3gnn_dataset_arrays;
+/* The buffers of one batch (DEVICE, caller-owned), in the keys, dtypes and
+ * layouts of the Python collate: x int64 [atom_cap], edge_index int64
+ * [2][edge_cap] (batch rows), edge_vec / pbc_shift f32 [edge_cap][3] (pbc_shift
+ * unread, may be NULL, when the dataset holds no shifts), force_of_atoms f32
+ * [atom_cap][3], batch int64 [atom_cap], num_atoms int64 [slots], cell_volume /
+ * total_energy f32 [slots], stress f32 [slots][6]. */
+typedef struct {
+  int64_t* x;
+  int64_t* edge_index;
+  float* edge_vec;
+  float* pbc_shift;
+  float* force_of_atoms;
+  int64_t* batch;
+  int64_t* num_atoms;
+  float* cell_volume;
+  float* total_energy;
+  float* stress;
+} e3gnn_batch_arrays;
+e3gnn_dataset* e3gnn_dataset_create(int device, int64_t n_structures, const int64_t* atom_ptr,
+                                    const int64_t* edge_ptr, const e3gnn_dataset_arrays* arrays);
+void e3gnn_dataset_free(e3gnn_dataset* h);
+/* One padded batch: the structures index[0..n_real) (HOST int64; any order,
+ * repeats allowed) fill the first slots; the other slots - n_real >= 1 slots
+ * are dummies.  Every buffer is written in full:
+ *   atoms   real rows, then atom_cap - (real atoms) dummy atoms: type 0, NaN
+ *           force label; one per dummy slot, the last dummy slot takes the rest
+ *   edges   real edges (offset to batch rows), then edge_cap - (real edges)
+ *           padded edges: centre = neighbour = a dummy row, edge_vec
+ *           (r_pad, 0, 0), pbc_shift 0, dealt over the dummy atoms in blocks of
+ *           ceil(padded / dummy atoms) -- centres non-decreasing, so a batch of
+ *           CSR-sorted structures stays CSR-sorted
+ *   slots   dummy: total_energy and stress NaN, cell_volume 1
+ * One launch on `stream`; the call returns once it is enqueued (no
+ * synchronise, no device-to-host copy), and the per-batch slot table travels
+ * in the kernel arguments, so the next call may follow at once.  A gather:
+ * bitwise reproducible.  Refused before any HIP call (E3GNN_ERR_ARG, the
+ * message says which): NULL handle or buffers, slots outside [2, 64], more
+ * than slots - 1 real structures, an index outside [0, S), real atoms plus one
+ * per dummy slot above atom_cap, real edges above edge_cap, a dummy atom that
+ * would get more than max_degree padded edges, r_pad not finite or <= 0. */
+int e3gnn_dataset_collate(const e3gnn_dataset* h, int64_t n_real, const int64_t* index, int slots,
+                          int64_t atom_cap, int64_t edge_cap, int64_t max_degree, float r_pad,
+                          const e3gnn_batch_arrays* out, void* stream);
+
 /* ---- DFT-D3 dispersion ----
  * Replaces the reference's LAMMPS pair style d3 (sevenn/pair_e3gnn/pair_d3.cu):
  * e3gnn_d3_create = PairD3::settings + coeff (:265-307, :656-767),

@@ -31,7 +31,8 @@ SELF_CONNECTION_TEMP = 'self_cont_tmp'
 INFO = 'data_info'
 # this build: dE/dedge_vec per edge (ForceStressOutputFromEdge's intermediate)
 EDGE_GRAD = 'edge_grad'
-# this build: 0-dim bool tensor set by train.collate when edge_index is sorted
-# by centre (stable, on the host); the captured fine-tune step then skips its
-# device sort
+# this build: two-entry int64 HOST tensor (edge_index's data pointer and
+# version counter, train.mark_edges_sorted) set by train.collate and the device
+# loader when edge_index is sorted by centre; the captured fine-tune step then
+# skips its device sort.  It stays on the host when a batch moves.
 EDGE_SORTED = 'edge_index_centre_sorted'

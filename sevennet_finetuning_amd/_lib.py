@@ -109,6 +109,10 @@ SIGNATURES = {
     'e3gnn_nlist_batch_build': (_c_int, [_vp, _c_i64, _P(_c_i64), _vp, _P(ctypes.c_double),
                                          _P(ctypes.c_int32), ctypes.c_double, _P(_c_i64), _vp]),
     'e3gnn_nlist_batch_fetch': (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'e3gnn_dataset_create': (_vp, [_c_int, _c_i64, _P(_c_i64), _P(_c_i64), _vp]),
+    'e3gnn_dataset_free': (None, [_vp]),
+    'e3gnn_dataset_collate': (_c_int, [_vp, _c_i64, _P(_c_i64), _c_int, _c_i64, _c_i64, _c_i64,
+                                       _c_f, _vp, _vp]),
     'e3gnn_set_impl':(_c_int, [_vp, _c_int]),
     'e3gnn_set_timing': (_c_int, [_vp, _c_int]),
     'e3gnn_set_stream_ordered': (_c_int, [_vp, _c_int]),
@@ -149,6 +153,18 @@ class ColsumDesc(ctypes.Structure):
     """e3gnn_colsum_desc (include/e3gnn.h)"""
     _fields_ = [('src', _vp), ('dst', _vp), ('ld', _c_i64), ('rows', ctypes.c_int32),
                 ('cols', ctypes.c_int32)]
+
+
+class DatasetArrays(ctypes.Structure):
+    """e3gnn_dataset_arrays (include/e3gnn.h)"""
+    _fields_ = [(k, _vp) for k in ('type', 'force', 'edge_center', 'edge_nbr', 'edge_vec', 'shift',
+                                   'energy', 'stress', 'volume')]
+
+
+class BatchArrays(ctypes.Structure):
+    """e3gnn_batch_arrays (include/e3gnn.h)"""
+    _fields_ = [(k, _vp) for k in ('x', 'edge_index', 'edge_vec', 'pbc_shift', 'force_of_atoms',
+                                   'batch', 'num_atoms', 'cell_volume', 'total_energy', 'stress')]
 
 
 class E3GNNError(RuntimeError):

@@ -1,6 +1,6 @@
 // Error plumbing shared by the translation units behind the C ABI of
 // include/e3gnn.h (api.cpp, model_load.cpp, api_train.cpp, api_nlist.cpp,
-// api_d3.cpp): one thread-local last-error string for the whole library
+// api_d3.cpp, api_data.cpp): one thread-local last-error string for the whole library
 // (defined in api.cpp, read by e3gnn_last_error).
 #pragma once
 #include <hip/hip_runtime.h>

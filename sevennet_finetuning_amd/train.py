@@ -675,11 +675,23 @@ class Trainer:
         self.optimizer.step()
         return loss.detach(), mem_loss.detach()
 
+    def _to_device(self, batch, non_blocking=False):
+        """The batch on the trainer's device with its EDGE_SORTED flag still
+        valid: the flag (a host tensor naming the edge_index storage) stays on
+        the host, and a move that copied edge_index re-marks the copy.  Host
+        checks only: no device sort later, no synchronisation here."""
+        was_sorted = edges_marked_sorted(batch)
+        out = {k: v if k == KEY.EDGE_SORTED else v.to(self.device, non_blocking=non_blocking)
+               for k, v in batch.items()}
+        if was_sorted and out[KEY.EDGE_IDX] is not batch[KEY.EDGE_IDX]:
+            mark_edges_sorted(out)
+        return out
+
     def run_one_epoch(self, loader, is_train=False):
         self.model.train(is_train)
         losses = []
         for batch in loader:
-            batch = {k: v.to(self.device, non_blocking=True) for k, v in batch.items()}
+            batch = self._to_device(batch, non_blocking=True)
             if is_train:
                 losses.append(self.train_step(batch)[0])
             else:
@@ -696,8 +708,8 @@ class Trainer:
             except StopIteration:
                 mem_iter = iter(memloader)
                 batch_mem = next(mem_iter)
-            batch = {k: v.to(self.device) for k, v in batch.items()}
-            batch_mem = {k: v.to(self.device) for k, v in batch_mem.items()}
+            batch = self._to_device(batch)
+            batch_mem = self._to_device(batch_mem)
             if is_train:
                 out.append(self.rehearsal_step(batch, batch_mem))
             else:
@@ -724,7 +736,7 @@ class Trainer:
         cnt = 0
         for batch in loader:
             self.zero_grad()
-            batch = {k: v.to(self.device) for k, v in batch.items()}
+            batch = self._to_device(batch)
             total = self.total_loss(self.model(batch))
             if loss_thr < 0 or total < loss_thr:
                 self.backward(total)
@@ -761,6 +773,9 @@ class GraphedRehearsalStep:
         # each captured shape keeps its own memory pool: beyond max_graphs
         # distinct shapes (variable-size datasets) new shapes run eagerly
         self.max_graphs = int(max_graphs)
+        # steps by path (captured: those that captured a new signature, which
+        # also replay it) and device argsorts of batches not marked sorted
+        self.stats = {'captured': 0, 'replayed': 0, 'eager': 0, 'device_sorts': 0}
 
     @staticmethod
     def _sig(b):
@@ -855,13 +870,19 @@ class GraphedRehearsalStep:
         return out
 
     def __call__(self, batch, mem):
+        given = (batch, mem)
         batch, mem = self._centre_sorted(batch), self._centre_sorted(mem)
+        self.stats['device_sorts'] += (batch is not given[0]) + (mem is not given[1])
         key = (self._sig(batch), self._sig(mem))
         ent = self.cache.get(key)
         if ent is None:
             if len(self.cache) >= self.max_graphs:
+                self.stats['eager'] += 1
                 return self.tr._rehearsal_body(batch, mem)
             ent = self.cache[key] = self._capture(batch, mem)
+            self.stats['captured'] += 1
+        else:
+            self.stats['replayed'] += 1
         # the batch tensors into the graph's static inputs: one multi-tensor
         # copy per dtype (a copy launch per tensor was ~26 launches a step)
         groups = {}
