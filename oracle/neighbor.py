@@ -6,6 +6,12 @@ i == j with zero shift): edge_index[0] = i (centre), edge_index[1] = j
 (neighbor), shift S (integer image, so pos[j] + S @ cell - pos[i] = r_ij),
 all images with |r_ij| < cutoff.  Edges sorted by i, then j, then S.
 O(N^2 * images): for small cells only.
+
+Only the images |S_k| <= ceil(cutoff / height_k) are enumerated, which covers
+every edge only for positions wrapped into the cell that is passed (fractional
+coordinates in [0, 1)).  With unwrapped positions (an equivalent, unreduced
+lattice around the atoms of the original cell, MD-style coordinates) edges
+whose shift lies beyond that range are silently missing: pass the wrapped copy.
 """
 import itertools
 

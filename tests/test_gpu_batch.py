@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import _cells as C
 from _systems import load_manifest_symbols, oracle_eval, system
 from sevennet_finetuning_amd.neighbor import batch_neighbor_list
 from sevennet_finetuning_amd.structures import CHEMICAL_SYMBOLS, Atoms, si_diamond
@@ -122,6 +123,26 @@ def test_batch_graph_is_reproducible(dnl, S):
     b = dnl.batch([x[1] for x in S], [x[2] for x in S], 5.0, [x[3] for x in S])
     for u, w in zip(a, b):
         assert torch.equal(u, w)
+
+
+def test_batch_graph_awkward_cells(dnl):
+    """The cells of tests/_cells.py in one batch: per-structure geometry, bins
+    and stencils of k_nlb_search on a sheared cell, an unreduced lattice (R > 1
+    on one axis), a halved bin grid, and degrees 64 and 512 (the cap) beside
+    them.  The host lists they are compared with equal the brute force
+    (tests/test_cells_host.py)."""
+    si = SYMS.index('Si')
+    S2 = []
+    for name, (pos, cell, _), pbc in (('sheared', C.sheared_hfo2(), T3),
+                                      ('relabelled', C.relabelled_hfo2(wrap=True), T3),
+                                      ('sparse_box', C.sparse_box(), T3),
+                                      ('ball65', C.ball(65), F3), ('ball513', C.ball(513), F3)):
+        S2.append((name, pos, cell, pbc, np.full(len(pos), si)))
+    c, n, s, _ = check_graph(dnl, S2, 5.0)
+    deg = np.bincount(c.cpu().numpy(), minlength=96 + 96 + 3 + 65 + 513)
+    assert np.array_equal(deg[192:195], [1, 1, 0])
+    assert np.all(deg[195:260] == 64) and np.all(deg[260:] == 512)
+    assert int(s[:int(deg[:192].sum())].abs().max()) >= 2
 
 
 # -------------------------------------------------------------- 2. refusals

@@ -5,10 +5,19 @@ tests/test_d3.py).  Needs an MI355X: ``pytest -m gpu``.
 Tolerances (fp32 pair terms as in the reference, fp64 row sums, vs fp64):
 energy 1e-5 relative, forces 1e-4 of the largest force component + 1e-6 eV/A,
 virial 1e-5 of the largest component.  Bitwise run-to-run determinism.
+
+The cell-list cases at the end (tests/_cells.py; their conditions are checked
+in tests/test_cells_host.py) run at short cutoffs, where one boundary cell of
+the stencil carries ~1e-3 of the energy.  Mixed boundaries: along a free axis
+the kernel does not wrap, while the reference and the oracle wrap all three
+axes (pair_d3.cu:1213-1218); the three agree for atoms inside the cell along
+the free axes, which is all these tests use -- nothing is asserted about atoms
+outside it.
 """
 import numpy as np
 import pytest
 
+import _cells as C
 from _systems import GOLD
 from oracle import d3_ref as D
 from sevennet_finetuning_amd.structures import si_diamond, mixed_symbols, CHEMICAL_SYMBOLS
@@ -138,8 +147,16 @@ def test_per_item_c6_path_matches_table_path(monkeypatch):
 def test_multi_bin_traversal_matches_oracle(monkeypatch, bin_bohr):
     """Small bins (E3GNN_D3_BIN) put several bins along every axis of these
     small cells, so the stencil walk, the image arithmetic of out-of-cell bins
-    and the centre-distance culling are all exercised against the oracle
-    (the default 30-bohr bins give one bin per axis below ~16 A)."""
+    and the centre-distance culling all run (the default 30-bohr bins give one
+    bin per axis below ~16 A).  What these cutoffs can detect: a gross error,
+    i.e. cells dropped or counted twice well inside the cutoff sphere, a wrong
+    image vector, a wrong bin index.  What they cannot: an error near the
+    cutoff.  At rthr 3000 the outer 10 % of the sphere (in r^2) carries 2.8e-4
+    of the energy over ~800 cells at 5 bohr (~46 at 13 bohr), so one missing
+    boundary cell of the stencil, a prune or cull radius short by a bin
+    diagonal, or a wrong image for an outermost cell moves the energy by 4e-7
+    to 6e-6 relative, under the 1e-5 bar.  The short-cutoff cases below
+    (test_short_cutoffs_small_bins and after) are the ones that see those."""
     monkeypatch.setenv('E3GNN_D3_BIN', bin_bohr)
     d = np.load(f'{GOLD}/hfo2_resdat.npz')
     z = np.array([CHEMICAL_SYMBOLS.index(str(s)) for s in d['symbols']])
@@ -200,3 +217,114 @@ def test_sevennet_d3_calculator_molecule():
     assert abs(b['energy'] - ref['energy']) <= 1e-5 * abs(ref['energy'])
     assert abs(both.results['energy'] - (a.results['energy'] + b['energy'])) < 1e-6
     assert np.allclose(both.results['forces'], a.results['forces'] + b['forces'], atol=1e-6)
+
+
+# ------------------------------------------------------------ cell-list cases
+# tests/_cells.py D3_CASES at short cutoffs: the outer 10 % of the cutoff sphere
+# carries 4e-3 to 2e-2 of the energy in a few tens of cells, so one dropped
+# stencil cell is ~1e-3, a hundred times _compare's energy bar.
+_ORACLE = {}
+
+
+def _case_oracle(name, damping):
+    """The oracle of a D3_CASES row, computed once per (row, damping)."""
+    if (name, damping) not in _ORACLE:
+        pos, cell, z, pbc, kw = C.d3_case(name)
+        _ORACLE[name, damping] = _oracle(pos, cell, z, damping, 'pbe', pbc, **kw)
+    return _ORACLE[name, damping]
+
+
+def _run_case(name, damping):
+    pos, cell, z, pbc, kw = C.d3_case(name)
+    got, _, _ = _hip(pos, cell, z, damping, 'pbe', pbc, **kw)
+    print(f'{name} {damping}: ', end='')
+    _compare(got, _case_oracle(name, damping))
+    return got
+
+
+def _set_bin(monkeypatch, bin_bohr):
+    if bin_bohr is None:
+        monkeypatch.delenv('E3GNN_D3_BIN', raising=False)
+    else:
+        monkeypatch.setenv('E3GNN_D3_BIN', bin_bohr)
+
+
+DAMPINGS = ['damp_bj', 'damp_zero']
+
+
+@pytest.mark.parametrize('damping', DAMPINGS)
+@pytest.mark.parametrize('bin_bohr', ['4', '7', None])
+@pytest.mark.parametrize('name', ['hfo2', 'sheared'])
+def test_short_cutoffs_small_bins(monkeypatch, name, bin_bohr, damping):
+    """Jittered HfO2 and the sheared cell (heights 7.8-10.3 A against lengths
+    10.1-12.1 A): with 4- and 7-bohr bins the stencil prune and the per-atom
+    cull act on cells whose pairs carry weight."""
+    _set_bin(monkeypatch, bin_bohr)
+    _run_case(name, damping)
+
+
+@pytest.mark.parametrize('damping', DAMPINGS)
+@pytest.mark.parametrize('bin_bohr', ['4', None])
+def test_unreduced_lattice(monkeypatch, bin_bohr, damping):
+    """The crystal of 'hfo2' in the equivalent lattice M cell (heights 2.7 /
+    7.3 / 10.3 A against lengths 10.1 / 24.3 / 16.8 A), with the positions
+    wrapped into it and as they were: against the oracle, and against the
+    kernel's own result on the original cell (the bars of
+    test_deterministic_and_wrap_invariant)."""
+    _set_bin(monkeypatch, bin_bohr)
+    base = _run_case('hfo2', damping)
+    for name in ('relabelled', 'relabelled_unwrapped'):
+        got = _run_case(name, damping)
+        de = abs(got['energy'] - base['energy'])
+        df = np.abs(got['forces'] - base['forces']).max()
+        print(f'{name} vs original cell: dE/E {de / abs(base["energy"]):.2e}  max|dF| {df:.2e}')
+        assert de < 1e-6 * abs(base['energy'])
+        assert df < 1e-5
+
+
+@pytest.mark.parametrize('damping', DAMPINGS)
+def test_several_default_bins_on_one_axis(monkeypatch, damping):
+    """HfO2 tiled (1, 1, 4): nb = (1, 1, 2) at the default 30-bohr bin edge,
+    with the C6 table and with the per-item C6 path."""
+    monkeypatch.delenv('E3GNN_D3_BIN', raising=False)
+    monkeypatch.delenv('E3GNN_D3_NO_C6TAB', raising=False)
+    _run_case('tiled', damping)
+    monkeypatch.setenv('E3GNN_D3_NO_C6TAB', '1')
+    _run_case('tiled', damping)
+
+
+@pytest.mark.parametrize('damping', DAMPINGS)
+@pytest.mark.parametrize('bin_bohr', ['4', None])
+@pytest.mark.parametrize('name', ['slab_ttf', 'wire_tff', 'slab_ftt'])
+def test_mixed_boundaries(monkeypatch, name, bin_bohr, damping):
+    """Slab and wire on the sheared cell, every atom inside the cell along the
+    free axes (see the module docstring): one bin and no image along a free
+    axis, several bins along the periodic ones at 4 bohr, prune and cull off.
+    Short cutoffs, then the default rthr / cn_thr."""
+    _set_bin(monkeypatch, bin_bohr)
+    _run_case(name, damping)
+    pos, cell, z, pbc, _ = C.d3_case(name)
+    got, _, _ = _hip(pos, cell, z, damping, 'pbe', pbc)
+    key = (name, damping, 'default')
+    if key not in _ORACLE:
+        _ORACLE[key] = _oracle(pos, cell, z, damping, 'pbe', pbc)
+    print(f'{name} {damping} default cutoffs: ', end='')
+    _compare(got, _ORACLE[key])
+
+
+@pytest.mark.parametrize('damping', DAMPINGS)
+def test_slab_virial_is_inplane_strain_derivative(damping):
+    """The slab's virial against -dE/d(strain) of the oracle by central
+    differences, for the three strains in the plane of the periodic vectors
+    (tests/test_d3.py does this for the bulk oracle).  Bar: _compare's virial
+    bar, 1e-5 of the largest component, plus 1e-6 of it for the difference
+    quotient (step 2e-6: no pair crosses a cutoff, see
+    tests/test_cells_host.py; rounding 2.2e-16 |E| / 2e-6 ~ 1e-10 |E|)."""
+    pos, cell, z, pbc, kw = C.d3_case('slab_ttf')
+    got, _, _ = _hip(pos, cell, z, damping, 'pbe', pbc, **kw)
+    scale = np.abs(_case_oracle('slab_ttf', damping)['virial']).max()
+    w = C.virial33(got['virial'])
+    for eps, want in C.inplane_strain_derivatives(pos, cell, z, damping, pbc, kw):
+        err = abs(np.sum(eps * w) - want)
+        print(f'slab {damping}: eps:W {np.sum(eps * w):.6f}  -dE/ds {want:.6f}  diff {err:.2e}')
+        assert err < 1.1e-5 * scale

@@ -1,10 +1,17 @@
 """Device neighbour list (e3gnn_nlist_*, csrc/neighbor.hip) vs the host list
 and the oracle's brute force: identical edges, order and integer shifts (bit
-for bit), edge vectors within f32 rounding.  Needs an MI355X: ``pytest -m gpu``."""
+for bit), edge vectors within f32 rounding.  Needs an MI355X: ``pytest -m gpu``.
+
+The cell-list cases at the end take their geometries from tests/_cells.py;
+tests/test_cells_host.py checks on the CPU that the host list equals the brute
+force on them.  oracle/neighbor.py is right only for positions wrapped into
+the cell, so ``brute=True`` gets wrapped copies and unwrapped positions are
+compared with the host list."""
 import numpy as np
 import pytest
 import torch
 
+import _cells as C
 from sevennet_finetuning_amd.neighbor import neighbor_list
 from sevennet_finetuning_amd.structures import si_diamond
 
@@ -132,3 +139,77 @@ def test_energy_forces_from_device_list(dnl):
                             torch.tensor(ei[1], device='cuda:0'), vec)
     assert abs(float(a['energy']) - float(b['energy'])) <= 1e-6 * abs(float(b['energy']))
     assert (a['forces'] - b['forces']).abs().max().item() <= 1e-5
+
+
+# ------------------------------------------------------------ cell-list cases
+def test_sheared_cell_vs_bruteforce(dnl):
+    """Heights 7.8 / 9.8 / 10.3 A against lengths 10.1 / 12.1 / 11.4 A."""
+    pos, cell, _ = C.sheared_hfo2()
+    check(dnl, pos, cell, brute=True)
+
+
+@pytest.mark.parametrize('rc', [5.0, 6.0])
+def test_unreduced_lattice_vs_bruteforce(dnl, rc):
+    """Heights 2.7 / 7.3 / 10.3 A against lengths 10.1 / 24.3 / 16.8 A: two
+    heights below the cutoff, R = (2, 1, 1) and (3, 1, 1) bins of stencil."""
+    pos, cell, _ = C.relabelled_hfo2(wrap=True)
+    ei, _ = check(dnl, pos, cell, rc=rc, brute=True)
+    if rc == 5.0:
+        assert ei.shape[1] == 4302
+
+
+def test_unreduced_lattice_unwrapped(dnl):
+    """The atoms of the original cell in the unreduced lattice: the shifts
+    absorb fractional coordinates from -1.1 to 3.1 and reach |S| = 5."""
+    pos, cell, _ = C.relabelled_hfo2(wrap=False)
+    ei, sh = check(dnl, pos, cell)
+    assert ei.shape[1] == 4302 and np.abs(sh).max() == 5
+
+
+def test_bins_of_more_than_64_atoms(dnl):
+    """700 atoms in 2 x 2 x 2 bins (~87 each: the second trip of the 64-lane
+    loop over a bin), degrees 281..349 (sort tiles of 512)."""
+    pos, cell, _ = C.dense_box()
+    ei, _ = check(dnl, pos, cell)
+    deg = np.bincount(ei[0], minlength=len(pos))
+    assert ei.shape[1] == 221406 and deg.max() == 349
+
+
+def test_few_atoms_in_a_large_cell(dnl):
+    """Three atoms in a 60 A cube: 12^3 bins halved down to 3 x 3 x 6 (at most
+    4 n + 64); the only edges are 0 <-> 1 across the x boundary."""
+    pos, cell, _ = C.sparse_box()
+    ei, sh = check(dnl, pos, cell)
+    assert np.array_equal(ei, [[0, 1], [1, 0]])
+    assert np.array_equal(sh, [[-1, 0, 0], [1, 0, 0]])
+    check(dnl, pos, cell, brute=True)
+
+
+def test_many_bins_on_one_axis(dnl):
+    """HfO2 tiled (1, 1, 4): 8 bins along c, 1 and 2 along a and b."""
+    pos, cell, _ = C.tiled_hfo2()
+    ei, _ = check(dnl, pos, cell, brute=True)
+    assert ei.shape[1] == 4 * 4302
+
+
+@pytest.mark.parametrize('N', [64, 65, 66, 128, 129, 257, 513])
+def test_complete_graph_degrees_at_the_sort_padding(dnl, N):
+    """Every centre has degree N - 1 = 63, 64, 65, 127, 128, 256, 512: the
+    bitonic sort's padding below, at and above a power of two, and the cap
+    itself accepted.  The list is the full off-diagonal pair list in (i, j) order."""
+    pos, _, _ = C.ball(N)
+    ei, sh = check(dnl, pos, None, pbc=(False, False, False))
+    ii, jj = np.nonzero(~np.eye(N, dtype=bool))
+    assert np.array_equal(ei, np.stack([ii, jj]))
+    assert not sh.any()
+
+
+def test_degree_513_is_refused(dnl):
+    """One neighbour past the cap: a handled refusal from the single-structure
+    build, and the handle stays usable."""
+    from sevennet_finetuning_amd._lib import E3GNNError
+    pos, _, _ = C.ball(514)
+    with pytest.raises(E3GNNError, match='512'):
+        dnl(pos, None, 5.0, (False, False, False))
+    pos, cell, _ = C.sparse_box()
+    check(dnl, pos, cell)
