@@ -589,6 +589,50 @@ int e3gnn_nlist_batch_build(e3gnn_nlist* h, int64_t B, const int64_t* atom_ptr, 
 int e3gnn_nlist_batch_fetch(e3gnn_nlist* h, int32_t* edge_center, int32_t* edge_nbr, int32_t* shift,
                             float* edge_vec, int64_t* edge_ptr, void* stream);
 
+/* ---- cutoff filter over a host code's neighbour list ----
+ * The host loop of pair_e3gnn.cpp:156-182 on the device, over the list the
+ * host code (LAMMPS) already built at cutoff + skin: graph row t has the centre
+ * atom row_atom[t] and the candidates cand[cand_ptr[t] .. cand_ptr[t+1]); every
+ * candidate j (masked with neighmask: LAMMPS' special bits) with
+ * |x[j] - x[centre]|^2 < cutoff^2 (f64, the host loop's operation order) is an
+ * edge: edge_center = t, edge_nbr = atom_row[j], edge_vec = (float)(x[j] -
+ * x[centre]).  Atoms are the host code's indices (owned rows, then ghost rows
+ * whose x already holds the image), so no box and no periodicity enter.  Rows
+ * follow one another and a row's edges keep the list's order: nothing is
+ * sorted, there is no per-row limit, and the output is bitwise the host
+ * loop's.
+ * e3gnn_plist_create makes no HIP call (the device is first used by _set).
+ * e3gnn_plist_set takes HOST arrays -- row_atom int32 [n], cand_ptr int64
+ * [n+1], cand int32 [cand_ptr[n]] (raw entries), atom_row int32 [n_total] --
+ * checks them and copies them to the device through a pinned buffer
+ * (synchronises `stream`).  The list rules: cand_ptr[0] = 0 and non-decreasing,
+ * every masked candidate and every row_atom in [0, n_total), every atom_row in
+ * [0, n), atom_row[row_atom[t]] = t; a violation is E3GNN_ERR_ARG naming the
+ * row, before any launch, so the kernel indexes without guards.
+ * e3gnn_plist_check_list is that check alone (host only, no device).
+ * e3gnn_plist_build (any number of times after one set; x: DEVICE f64
+ * [n_total][3], kept alive and unchanged until the fetch, which repeats the
+ * test to place the edges) counts the edges and scans the row
+ * offsets (synchronises `stream`); E3GNN_ERR_GRAPH for 2^31 edges or more.
+ * e3gnn_plist_fetch writes edge_center / edge_nbr int32 [E] and edge_vec f32
+ * [E][3], DEVICE memory the caller sized from *n_edges (enqueued on `stream`,
+ * no synchronise).  The argument rules (NULL handle or arrays, n <= 0, n_total
+ * < n, either >= 2^30, a cutoff that is not positive and finite, build before
+ * set, fetch before build) are checked before any HIP call. */
+typedef struct e3gnn_plist e3gnn_plist;
+e3gnn_plist* e3gnn_plist_create(int device);
+void e3gnn_plist_free(e3gnn_plist* h);
+int e3gnn_plist_check_list(int64_t n, int64_t n_total, const int32_t* row_atom,
+                           const int64_t* cand_ptr, const int32_t* cand, int32_t neighmask,
+                           const int32_t* atom_row);
+int e3gnn_plist_set(e3gnn_plist* h, int64_t n, int64_t n_total, const int32_t* row_atom,
+                    const int64_t* cand_ptr, const int32_t* cand, int32_t neighmask,
+                    const int32_t* atom_row, void* stream);
+int e3gnn_plist_build(e3gnn_plist* h, const double* x, double cutoff, int64_t* n_edges,
+                      void* stream);
+int e3gnn_plist_fetch(e3gnn_plist* h, int32_t* edge_center, int32_t* edge_nbr, float* edge_vec,
+                      void* stream);
+
 /* ---- device-resident training dataset and batch assembly ----
  * Replaces the host side of the reference's training input: the graph list of
  * sevenn/train/dataload.py:71-140 held on the device, and PyG's Collater

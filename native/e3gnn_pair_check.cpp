@@ -24,14 +24,25 @@
 // (against the library's e3gnn_atom_virial on the whole box, matched by tag),
 // vatom_sum_max_diff (sum over atoms against the style's global virial),
 // vatom_max_ends (most edge ends on one atom) and vatom_repeat_bitwise.
+// With --graph-device style (1) then runs again on one rank in both graph
+// modes (pair_style e3gnn graph host|device) on the same atoms and list, and
+// the line gains the object graph_device: edges / edges_host, energy_, forces_
+// and virial_bits_equal (memcmp against the host mode), repeat_bitwise, and a
+// reuse leg -- every atom and image moved by up to 0.4 A per component keyed
+// by its tag, neighbor->ago = 1, the list left alone -- as reuse_edges,
+// reuse_edges_changed and reuse_bits_equal.  --time K runs style (1) only and
+// prints, per mode (host; device with the list re-uploaded; device with the
+// list reused), the median and range of K alternating compute() times in ms.
 //
 //   e3gnn_pair_check <model dir> <structure> <px> <py> <pz> [seed] [--gpu-aware] [--vatom]
+//                    [--graph-device] [--time K]
 //   structure: si:<cells> (displaced Si diamond) or a file
 //              "n \n 9 cell values (rows = lattice vectors) \n symbol x y z ..."
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <array>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -290,25 +301,203 @@ RunOut run(const Structure& S, const std::string& dir, const int grid[3], bool p
   return R;
 }
 
+// Style (1) on one rank, kept alive between force evaluations (--graph-device,
+// --time): the setup of run_rank, one list build, then compute() as often as
+// the caller likes, in either graph mode, with neighbor->ago in its hands.
+struct SerialRig {
+  LAMMPS lmp;
+  Memory mem;
+  Error err;
+  Atom atom;
+  Neighbor neigh;
+  Force force;
+  Domain dom;
+  World world{1};
+  std::unique_ptr<CommBrick> comm;
+  std::unique_ptr<PairE3GNN> pair;
+  NeighList list;
+  struct Result {
+    double energy = 0, virial[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<double> f;   // owned atoms
+    long long edges = 0;
+    bool same_bits(const Result& o) const {
+      return !std::memcmp(&energy, &o.energy, 8) && !std::memcmp(virial, o.virial, 48) &&
+             f.size() == o.f.size() && !std::memcmp(f.data(), o.f.data(), f.size() * 8);
+    }
+  };
+
+  SerialRig(const Structure& S, const std::string& model_dir) {
+    const int one[3] = {1, 1, 1};
+    lmp.memory = &mem;
+    lmp.error = &err;
+    lmp.atom = &atom;
+    lmp.neighbor = &neigh;
+    lmp.force = &force;
+    lmp.domain = &dom;
+    comm.reset(new CommBrick(&lmp, &world, 0, one));
+    lmp.comm = comm.get();
+    dom.set_cell(S.cell);
+    neigh.skin = SKIN;
+    for (int a = 0; a < S.n; ++a) {
+      double s[3], x[3];
+      dom.x2lamda(&S.pos[3 * a], s);
+      for (int d = 0; d < 3; ++d) {
+        s[d] -= std::floor(s[d]);
+        if (s[d] >= 1.0) s[d] -= 1.0;
+      }
+      dom.lamda2x(s, x);
+      atom.add(x, s, S.tag[a], S.type[a]);
+    }
+    atom.nlocal = (int)atom.tags.size();
+    atom.natoms = S.n;
+    atom.ntypes = (int)S.elements.size();
+    atom.sync();
+    std::vector<std::string> args = {"*", "*", model_dir};
+    for (const auto& e : S.elements) args.push_back(e);
+    std::vector<char*> argv;
+    for (auto& a : args) argv.push_back(&a[0]);
+    pair.reset(new PairE3GNN(&lmp));
+    pair->settings(0, nullptr);
+    pair->coeff((int)argv.size(), argv.data());
+    pair->init_style();
+    const double cut = pair->init_one(1, 1);
+    comm->setup(cut + SKIN);
+    comm->borders();
+    neigh.build_full(&atom, cut, &list);
+    pair->init_list(0, &list);
+  }
+  void graph(const char* where) {
+    std::string a = "graph", b = where;
+    char* argv[2] = {&a[0], &b[0]};
+    pair->settings(2, argv);
+  }
+  void zero_forces() { std::fill(atom.fs.begin(), atom.fs.end(), 0.0); }
+  Result compute(int ago) {
+    neigh.ago = ago;
+    zero_forces();
+    pair->compute(1 | 2, 1);
+    Result r;
+    r.energy = pair->eng_vdwl;
+    std::copy(pair->virial, pair->virial + 6, r.virial);
+    r.f.assign(atom.fs.begin(), atom.fs.begin() + 3 * (size_t)atom.nlocal);
+    r.edges = pair->last_edges();
+    return r;
+  }
+  // every atom, owned or ghost, moved by a displacement keyed by its tag
+  // (|d| <= amp per component): every image of an atom moves alike
+  void displace(unsigned seed, double amp) {
+    const int nt = atom.nlocal + atom.nghost;
+    for (int a = 0; a < nt; ++a) {
+      std::mt19937 r(seed * 7919u + (unsigned)atom.tag[a]);
+      std::uniform_real_distribution<double> u(-amp, amp);
+      for (int k = 0; k < 3; ++k) atom.x[a][k] += u(r);
+    }
+  }
+};
+
+// --graph-device: the keys of the "graph_device" object
+std::string graph_device_keys(const Structure& S, const std::string& dir, unsigned seed) {
+  SerialRig rig(S, dir);
+  const auto host = rig.compute(0);
+  rig.graph("device");
+  const auto dev = rig.compute(0), dev2 = rig.compute(0);
+  // reuse leg: the atoms move, the list stays (ago = 1); device first, so that
+  // the step really reuses the list uploaded above
+  rig.displace(seed, 0.4);
+  const auto rdev = rig.compute(1);
+  rig.graph("host");
+  const auto rhost = rig.compute(1);
+  auto tf = [](bool b) { return b ? "true" : "false"; };
+  char buf[512];
+  std::snprintf(buf, sizeof(buf),
+                ", \"graph_device\": {\"edges\": %lld, \"edges_host\": %lld, \"energy_bits_equal\": %s, "
+                "\"forces_bits_equal\": %s, \"virial_bits_equal\": %s, \"repeat_bitwise\": %s, "
+                "\"reuse_edges\": %lld, \"reuse_edges_changed\": %s, \"reuse_bits_equal\": %s}",
+                dev.edges, host.edges, tf(!std::memcmp(&dev.energy, &host.energy, 8)),
+                tf(dev.f.size() == host.f.size() && !std::memcmp(dev.f.data(), host.f.data(), dev.f.size() * 8)),
+                tf(!std::memcmp(dev.virial, host.virial, 48)), tf(dev.same_bits(dev2)), rdev.edges,
+                tf(rdev.edges != dev.edges), tf(rdev.same_bits(rhost) && rdev.edges == rhost.edges));
+  return buf;
+}
+
+// --time K: style (1) only; per round host mode, device mode with the list
+// re-uploaded (ago = 0), device mode with the list reused (ago = 1)
+int time_graph_modes(const Structure& S, const std::string& dir, int K) {
+  using clk = std::chrono::steady_clock;
+  SerialRig rig(S, dir);
+  auto timed = [&](int ago) {
+    rig.neigh.ago = ago;
+    rig.zero_forces();
+    const auto t0 = clk::now();
+    rig.pair->compute(1, 1);   // ends in a stream synchronise
+    return std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+  };
+  for (int w = 0; w < 2; ++w) timed(0);
+  rig.graph("device");
+  for (int w = 0; w < 2; ++w) timed(0);
+  for (int w = 0; w < 2; ++w) timed(1);
+  std::vector<double> t[3];
+  int wins = 0;
+  for (int k = 0; k < K; ++k) {
+    rig.graph("host");
+    t[0].push_back(timed(0));
+    rig.graph("device");
+    t[1].push_back(timed(0));
+    t[2].push_back(timed(1));
+    wins += t[2].back() < t[0].back();
+  }
+  auto stats = [](std::vector<double> v) {
+    std::sort(v.begin(), v.end());
+    const size_t m = v.size();
+    const double med = m % 2 ? v[m / 2] : 0.5 * (v[m / 2 - 1] + v[m / 2]);
+    char buf[96];
+    std::snprintf(buf, sizeof(buf), "{\"median\": %.3f, \"min\": %.3f, \"max\": %.3f}", med, v.front(), v.back());
+    return std::string(buf);
+  };
+  auto rounds = [](const std::vector<double>& v) {
+    std::string s = "[";
+    char buf[32];
+    for (size_t k = 0; k < v.size(); ++k) {
+      std::snprintf(buf, sizeof(buf), "%s%.3f", k ? ", " : "", v[k]);
+      s += buf;
+    }
+    return s + "]";
+  };
+  std::printf("{\"n_atoms\": %d, \"ghosts\": %d, \"edges\": %lld, \"rounds\": %d, \"host_ms\": %s, "
+              "\"device_new_list_ms\": %s, \"device_reused_list_ms\": %s, \"reused_beats_host_rounds\": %d, "
+              "\"host_rounds_ms\": %s, \"device_new_list_rounds_ms\": %s, \"device_reused_list_rounds_ms\": %s}\n",
+              S.n, rig.atom.nghost, rig.pair->last_edges(), K, stats(t[0]).c_str(), stats(t[1]).c_str(),
+              stats(t[2]).c_str(), wins, rounds(t[0]).c_str(), rounds(t[1]).c_str(), rounds(t[2]).c_str());
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s model_dir structure px py pz [seed] [--gpu-aware] [--vatom]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s model_dir structure px py pz [seed] [--gpu-aware] [--vatom] "
+                         "[--graph-device] [--time K]\n", argv[0]);
     return 2;
   }
   const std::string dir = argv[1];
   const int grid[3] = {std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5])};
   unsigned seed = 0;
-  bool want_vatom = false;
+  bool want_vatom = false, want_graph_device = false;
+  int time_rounds = 0;
   for (int k = 6; k < argc; ++k) {
     if (!std::strcmp(argv[k], "--gpu-aware")) setenv("E3GNN_GPU_AWARE_MPI", "1", 1);
     else if (!std::strcmp(argv[k], "--vatom")) want_vatom = true;
+    else if (!std::strcmp(argv[k], "--graph-device")) want_graph_device = true;
+    else if (!std::strcmp(argv[k], "--time") && k + 1 < argc) time_rounds = std::max(1, std::atoi(argv[++k]));
     else seed = (unsigned)std::atoi(argv[k]);
   }
   try {
     std::mt19937 rng(seed);
     const Structure S = load_structure(argv[2], rng);
+    if (time_rounds) {
+      if (hipSetDevice(0) != hipSuccess) throw std::runtime_error("hipSetDevice");
+      return time_graph_modes(S, dir, time_rounds);
+    }
     e3gnn_pair::Model model(dir, 0);
     const std::vector<int> map = model.type_map(S.elements);
     const double rc = model.cutoff();
@@ -410,6 +599,7 @@ int main(int argc, char** argv) {
       return buf;
     };
     const std::string vs = vatom_keys(ser), vp = vatom_keys(par);
+    const std::string gd = want_graph_device ? graph_device_keys(S, dir, seed) : "";
     std::printf(
         "{\"n_atoms\": %d, \"ranks\": %d, \"energy_ref\": %.8f, \"max_virial_ref\": %.6e, "
         "\"serial\": {\"energy\": %.8f, \"energy_rel\": %.3e, \"max_force\": %.3e, \"max_virial\": %.3e, "
@@ -418,7 +608,7 @@ int main(int argc, char** argv) {
         "\"eatom_sum_rel\": %.3e, \"repeat_bitwise\": %s, \"vs_serial_energy_rel\": %.3e, "
         "\"vs_serial_max_force\": %.3e%s}, "
         "\"comm\": {\"ghosts\": %lld, \"swaps\": %lld, \"sent\": %lld, \"relayed\": %lld, \"extra_rows\": %lld, "
-        "\"zero_sends\": %lld, \"trash_forward\": %lld, \"trash_reverse\": %lld}}\n",
+        "\"zero_sends\": %lld, \"trash_forward\": %lld, \"trash_reverse\": %lld}%s}\n",
         n, grid[0] * grid[1] * grid[2], e_ref, std::max(std::fabs(*std::max_element(v_ref, v_ref + 6)),
                                                        std::fabs(*std::min_element(v_ref, v_ref + 6))),
         ser.energy, std::fabs(ser.energy - e_ref) / scale, max_diff(ser.f_tag, f_ref), max_vdiff(ser.virial, v_ref),
@@ -428,7 +618,8 @@ int main(int argc, char** argv) {
         std::fabs(par.energy - ser.energy) / scale, max_diff(par.f_tag, ser.f_tag), vp.c_str(),
         (long long)par.ghosts,
         (long long)par.st.swaps, (long long)par.st.sent, (long long)par.st.relayed, (long long)par.st.extra_rows,
-        (long long)par.st.zero_sends, (long long)par.st.trash_forward, (long long)par.st.trash_reverse);
+        (long long)par.st.zero_sends, (long long)par.st.trash_forward, (long long)par.st.trash_reverse,
+        gd.c_str());
   } catch (const std::exception& e) {
     std::fprintf(stderr, "e3gnn_pair_check: %s\n", e.what());
     return 1;

@@ -69,6 +69,8 @@ void PairE3GNN::compute(int eflag, int vflag)
   nv.nlocal = atom->nlocal;
   nv.nghost = atom->nghost;
   nv.neighmask = NEIGHMASK;
+  nv.list_age = neighbor->ago;   // 0 on the step the list was rebuilt
+  nv.x_flat = atom->x[0];        // Atom's x is one contiguous block (memory->create)
 
   e3gnn_pair::PairOut out;
   if (step->compute(nv, species, atom->f, eflag_atom ? eatom : nullptr, out, vflag_atom ? vatom : nullptr))
@@ -85,10 +87,19 @@ void PairE3GNN::allocate()
   memory->create(cutsq, n + 1, n + 1, "pair:cutsq");
 }
 
-void PairE3GNN::settings(int narg, char ** /*arg*/)
+// pair_style e3gnn [graph host|device]: where the step's graph is built
+// (e3gnn_pair::SerialStep::GraphBuild; host when absent)
+void PairE3GNN::settings(int narg, char **arg)
 {
-  if (narg != 0) error->all(FLERR, "Illegal pair_style command");
+  if (narg == 0) graph_device = 0;
+  else if (narg == 2 && strcmp(arg[0], "graph") == 0 && strcmp(arg[1], "host") == 0) graph_device = 0;
+  else if (narg == 2 && strcmp(arg[0], "graph") == 0 && strcmp(arg[1], "device") == 0) graph_device = 1;
+  else error->all(FLERR, "Illegal pair_style command");
+  if (step) step->set_graph_build(graph_device ? e3gnn_pair::SerialStep::GraphBuild::Device
+                                               : e3gnn_pair::SerialStep::GraphBuild::Host);
 }
+
+long long PairE3GNN::last_edges() const { return step ? (long long) step->last_edges() : 0; }
 
 // pair_coeff * * <deployment dir> <element of type 1> <element of type 2> ...
 void PairE3GNN::coeff(int narg, char **arg)
@@ -106,6 +117,7 @@ void PairE3GNN::coeff(int narg, char **arg)
     model.reset(new e3gnn_pair::Model(arg[2], device));
     species = model->type_map(elements);
     step.reset(new e3gnn_pair::SerialStep(*model));
+    if (graph_device) step->set_graph_build(e3gnn_pair::SerialStep::GraphBuild::Device);
   } catch (const std::exception &e) {
     error->all(FLERR, std::string("e3gnn: ") + e.what());
   }

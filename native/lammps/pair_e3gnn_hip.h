@@ -4,7 +4,7 @@
    libe3gnn_hip.so (include/e3gnn.h) through the LAMMPS-independent core
    native/pair_e3gnn_core.{h,cpp}.  Same style name, same input lines:
 
-     pair_style e3gnn
+     pair_style e3gnn [graph host|device]
      pair_coeff * * <deployment dir: weights.bin + manifest.json> <element per type>
 
    Build: copy this file, pair_e3gnn_core.{h,cpp} and include/e3gnn.h into
@@ -43,11 +43,13 @@ class PairE3GNN : public Pair {
   void coeff(int, char **) override;
   void init_style() override;
   double init_one(int, int) override;
+  long long last_edges() const;   // edges of the last compute()
 
  protected:
   void allocate();
   double cutoff = 0.0;
   int device = 0;
+  int graph_device = 0;   // pair_style e3gnn graph device
   std::unique_ptr<e3gnn_pair::Model> model;
   std::unique_ptr<e3gnn_pair::SerialStep> step;
   std::vector<int> species;   // LAMMPS type -> model species index

@@ -80,6 +80,7 @@ void Neighbor::build_full(Atom *atom, double cutforce, NeighList *list)
 {
   const int nl = atom->nlocal, nt = atom->nlocal + atom->nghost;
   const double c2 = (cutforce + skin) * (cutforce + skin);
+  ago = 0;
   list->inum = nl;
   list->ilist_s.resize(nl);
   list->numneigh_s.assign(nt, 0);

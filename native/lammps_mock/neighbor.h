@@ -13,6 +13,7 @@ class Neighbor {
  public:
   double skin = 1.0;
   int requested_full = 0;
+  int ago = 0;   // steps since the last list build
   NeighRequest *add_request(Pair *, int flags = 0)
   {
     requested_full = flags & NeighConst::REQ_FULL;

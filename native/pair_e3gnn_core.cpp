@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <fstream>
 #include <sstream>
 #include <stdexcept>
@@ -150,14 +151,26 @@ SerialStep::SerialStep(const Model& model) : model_(model) {
 
 SerialStep::~SerialStep() {
   g_.release();
+  if (x_dev_) (void)hipFree(x_dev_);
+  if (plist_) e3gnn_plist_free(plist_);
   if (stream_) (void)hipStreamDestroy((hipStream_t)stream_);
   if (ctx_) e3gnn_ctx_free(ctx_);
 }
 
+void SerialStep::set_graph_build(GraphBuild g) {
+  if (g != build_) list_valid_ = false;   // the host mode may have moved g_'s buffers
+  build_ = g;
+}
+
 int SerialStep::compute(const NeighborView& nv, const std::vector<int>& map, double** f,
                         double* eatom, PairOut& out, double** vatom) {
+  if (int rc = nodes(nv, map)) return rc;
+  if (int rc = build_ == GraphBuild::Device ? graph_device(nv) : graph_host(nv)) return rc;
+  return evaluate(nv.inum, f, eatom, out, vatom);
+}
+
+int SerialStep::nodes(const NeighborView& nv, const std::vector<int>& map) {
   const int n = nv.inum;
-  const double rc2 = model_.cutoff() * model_.cutoff();
   // nodes = tag - 1 (pair_e3gnn.cpp:146-154; "requires consecutive atom IDs")
   tag2i_.assign(n, -1);
   type_.assign(n, 0);
@@ -176,6 +189,12 @@ int SerialStep::compute(const NeighborView& nv, const std::vector<int>& map, dou
     tag2i_[t] = i;
     type_[t] = map[ty];
   }
+  return E3GNN_OK;
+}
+
+int SerialStep::graph_host(const NeighborView& nv) {
+  const int n = nv.inum;
+  const double rc2 = model_.cutoff() * model_.cutoff();
   // edges in node order (the kernels take edge_center sorted): every full-list
   // neighbour inside the cutoff (pair_e3gnn.cpp:156-182), edge_vec = x_j - x_i,
   // which is pos[jtag] - pos[itag] + shift @ cell exactly
@@ -217,6 +236,83 @@ int SerialStep::compute(const NeighborView& nv, const std::vector<int>& map, dou
     CORE_HIP(hipMemcpyAsync(g_.nbr, nbr_.data(), nedges_ * 4, hipMemcpyHostToDevice, s));
     CORE_HIP(hipMemcpyAsync(g_.vec, vec_.data(), nedges_ * 12, hipMemcpyHostToDevice, s));
   }
+  return E3GNN_OK;
+}
+
+// The same edges from the same list, filtered on the device (e3gnn_plist_*):
+// rows in tag order, each row's candidates in the list's order, the special
+// bits masked in the kernel.  The flattened list, atom_row = tag - 1 of every
+// owned and ghost atom and the types travel when the list is new; x every step.
+int SerialStep::graph_device(const NeighborView& nv) {
+  const int n = nv.inum;
+  const int64_t ntot = (int64_t)nv.nlocal + nv.nghost;
+  hipStream_t s = (hipStream_t)stream_;
+  if (!plist_) {
+    int dev = 0;
+    CORE_HIP(hipGetDevice(&dev));
+    plist_ = e3gnn_plist_create(dev);
+    if (!plist_) {
+      err_ = std::string("e3gnn_plist_create: ") + e3gnn_last_error();
+      return E3GNN_ERR_ARG;
+    }
+  }
+  const bool fresh = !list_valid_ || nv.list_age == 0 || nv.inum != up_inum_ ||
+                     nv.nlocal != up_nlocal_ || nv.nghost != up_nghost_ ||
+                     (const void*)nv.firstneigh != up_first_;
+  if (fresh) {
+    list_valid_ = false;
+    cand_ptr_.resize((size_t)n + 1);
+    cand_ptr_[0] = 0;
+    for (int t = 0; t < n; ++t) cand_ptr_[t + 1] = cand_ptr_[t] + nv.numneigh[tag2i_[t]];
+    cand_.resize((size_t)cand_ptr_[n] + 1);   // + 1: never a null pointer
+    for (int t = 0; t < n; ++t) {
+      const int i = tag2i_[t];
+      if (nv.numneigh[i] > 0)
+        std::memcpy(&cand_[cand_ptr_[t]], nv.firstneigh[i], (size_t)nv.numneigh[i] * sizeof(int));
+    }
+    atom_row_.resize((size_t)ntot);
+    for (int64_t a = 0; a < ntot; ++a) {
+      const int64_t r = nv.tag[a] - 1;
+      // out of range: a value e3gnn_plist_set refuses, naming the atom
+      atom_row_[a] = r >= 0 && r < n ? (int32_t)r : -1;
+    }
+    CORE_ABI(e3gnn_plist_set(plist_, n, ntot, tag2i_.data(), cand_ptr_.data(), cand_.data(),
+                             nv.neighmask, atom_row_.data(), s));
+    up_inum_ = nv.inum;
+    up_nlocal_ = nv.nlocal;
+    up_nghost_ = nv.nghost;
+    up_first_ = (const void*)nv.firstneigh;
+  }
+  if (ntot > x_cap_) {
+    if (x_dev_) CORE_HIP(hipFree(x_dev_));
+    x_dev_ = nullptr;
+    x_cap_ = ntot + ntot / 5 + 64;
+    CORE_HIP(hipMalloc(&x_dev_, (size_t)x_cap_ * 24));
+  }
+  const double* xh = nv.x_flat;
+  if (!xh) {
+    xpack_.resize(3 * (size_t)ntot);
+    for (int64_t a = 0; a < ntot; ++a) std::memcpy(&xpack_[3 * (size_t)a], nv.x[a], 24);
+    xh = xpack_.data();
+  }
+  CORE_HIP(hipMemcpyAsync(x_dev_, xh, (size_t)ntot * 24, hipMemcpyHostToDevice, s));
+  CORE_ABI(e3gnn_plist_build(plist_, x_dev_, model_.cutoff(), &nedges_, s));
+  try {
+    g_.reserve(n, nedges_);
+  } catch (const std::exception& e) {
+    err_ = e.what();
+    return E3GNN_ERR_HIP;
+  }
+  if (fresh) {
+    CORE_HIP(hipMemcpyAsync(g_.type, type_.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    list_valid_ = true;
+  }
+  CORE_ABI(e3gnn_plist_fetch(plist_, g_.center, g_.nbr, g_.vec, s));
+  return E3GNN_OK;
+}
+
+int SerialStep::evaluate(int n, double** f, double* eatom, PairOut& out, double** vatom) {
+  hipStream_t s = (hipStream_t)stream_;
   CORE_ABI(e3gnn_energy_forces(ctx_, n, nedges_, g_.type, g_.center, g_.nbr, g_.vec, g_.scalars,
                                eatom ? g_.atomic : nullptr, g_.forces, g_.scalars + 1, nullptr, s));
   if (vatom) CORE_ABI(e3gnn_atom_virial(ctx_, g_.vatom, s));

@@ -30,6 +30,8 @@ struct NeighborView {
   const int64_t* tag = nullptr;      // atom->tag (1..natoms; ghosts carry their owner's tag)
   int nlocal = 0, nghost = 0;
   int neighmask = 0x1FFFFFFF;        // NEIGHMASK
+  int list_age = 0;                  // neighbor->ago: steps since the host rebuilt the list (0: treat as new)
+  const double* x_flat = nullptr;    // atom->x[0] when the rows are contiguous; null: the core packs x
 };
 
 // LAMMPS' per-step accumulators of a pair style (Pair::eng_vdwl, virial[6],
@@ -83,10 +85,21 @@ struct DeviceGraph {
 // `vatom` (Pair::vatom, nullable): the per-atom virial of the edge-gradient
 // partition (e3gnn_atom_virial) ADDED to the owned atoms' rows in LAMMPS order
 // (xx, yy, zz, xy, xz, yz); rows are tags, so nothing is left on ghosts.
+//
+// The graph is built on the host (GraphBuild::Host, the default: the
+// reference's loop over the full list) or on the device (GraphBuild::Device:
+// e3gnn_plist_* filters the same list in the same order, so the edges and every
+// result are bitwise those of the host loop).  On the device the list itself
+// travels only when it is new (NeighborView::list_age == 0, or inum / nlocal /
+// nghost / firstneigh changed, or the mode was just switched); the steps in
+// between upload x alone.
 class SerialStep {
  public:
+  enum class GraphBuild { Host, Device };
   explicit SerialStep(const Model& model);
   ~SerialStep();
+  void set_graph_build(GraphBuild g);
+  GraphBuild graph_build() const { return build_; }
   // returns 0, or an E3GNN_ERR_* code with the message in error()
   int compute(const NeighborView& nv, const std::vector<int>& map, double** f, double* eatom,
               PairOut& out, double** vatom = nullptr);
@@ -103,6 +116,24 @@ class SerialStep {
   std::vector<int> tag2i_;
   int64_t nedges_ = 0;
   std::string err_;
+  // the three parts of compute: nodes (tags, types), edges on the device
+  // buffers g_, then the model and the scatter
+  int nodes(const NeighborView& nv, const std::vector<int>& map);
+  int graph_host(const NeighborView& nv);
+  int graph_device(const NeighborView& nv);
+  int evaluate(int n, double** f, double* eatom, PairOut& out, double** vatom);
+  // GraphBuild::Device: the list filter, the flattened list and what the last
+  // upload was made from
+  GraphBuild build_ = GraphBuild::Host;
+  e3gnn_plist* plist_ = nullptr;
+  bool list_valid_ = false;
+  int up_inum_ = -1, up_nlocal_ = -1, up_nghost_ = -1;
+  const void* up_first_ = nullptr;
+  std::vector<int64_t> cand_ptr_;
+  std::vector<int32_t> cand_, atom_row_;
+  std::vector<double> xpack_;
+  double* x_dev_ = nullptr;
+  int64_t x_cap_ = 0;
 };
 
 // pair_style e3gnn/parallel/hip (PairE3GNNParallel::compute,

@@ -17,10 +17,10 @@ CSRC = os.path.join(HERE, 'csrc')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 LIB = os.path.join(HERE, 'libe3gnn_hip.so')
 OBJDIR = os.path.join(HERE, 'csrc', 'build')
-SOURCES = ['api.cpp', 'model_load.cpp', 'api_train.cpp', 'api_nlist.cpp', 'api_d3.cpp', 'api_data.cpp',
+SOURCES = ['api.cpp', 'model_load.cpp', 'api_train.cpp', 'api_nlist.cpp', 'api_plist.cpp', 'api_d3.cpp', 'api_data.cpp',
            'collate.hip', 'generic.cpp',
            'gemm.hip', 'tp.hip', 'node.hip', 'fused.hip', 'neighbor.hip', 'd3.hip', 'train_ops.hip', 'gtp.hip', 'generic.hip', 'mlp_train.hip', 'tgemm.hip',
-           'fcn_train.hip', 'atom_virial.hip', 'segment_sum.hip']
+           'fcn_train.hip', 'atom_virial.hip', 'segment_sum.hip', 'pairlist.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', f'-I{INCLUDE}',
          '-Wall', '-Wno-unused-function']

@@ -292,3 +292,75 @@ class DeviceNeighborList:
                                                    'nbr', 'shift', 'vec')], s))
         out.update(n_local=nl, n_interior=ni, n_ghost=ng)
         return out
+
+
+class ListFilter:
+    """Cutoff filter over a neighbour list a host code already built
+    (libe3gnn_hip.so ``e3gnn_plist_*``): the loop of the serial LAMMPS pair
+    style on the device, for callers who hold a LAMMPS list (through the
+    ``lammps`` module, say).
+
+    ``set(row_atom, cand_ptr, cand, atom_row, neighmask)`` uploads the list
+    (host arrays): graph row t has the centre atom ``row_atom[t]`` and the
+    candidates ``cand[cand_ptr[t]:cand_ptr[t + 1]]`` (raw entries, masked with
+    ``neighmask``); ``atom_row[a]`` is the graph row of atom index a (owned or
+    ghost).  A list that breaks a rule raises ``E3GNNError`` naming the row.
+
+    ``__call__(x, cutoff)`` (any number of times after one ``set``; ``x`` f64
+    [n_total, 3]) returns device tensors ``(center int32 [E], nbr int32 [E],
+    vec float32 [E, 3])``: every candidate within the cutoff, rows one after
+    the other, each row in the list's order -- bitwise the host loop's edges."""
+
+    def __init__(self, device='cuda:0'):
+        import torch
+        from . import _lib
+        self._torch, self._L = torch, _lib
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        idx = self.device.index if self.device.index is not None else 0
+        self._h = self.lib.e3gnn_plist_create(idx)
+        if not self._h:
+            raise _lib.E3GNNError(self.lib.e3gnn_last_error().decode())
+        self.n_total = 0
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h:
+            self.lib.e3gnn_plist_free(h)
+
+    def set(self, row_atom, cand_ptr, cand, atom_row, neighmask=0x1FFFFFFF):
+        import ctypes
+        i32, i64 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+        row_atom = np.ascontiguousarray(row_atom, dtype=np.int32)
+        cand_ptr = np.ascontiguousarray(cand_ptr, dtype=np.int64)
+        cand = np.ascontiguousarray(cand, dtype=np.int32)
+        atom_row = np.ascontiguousarray(atom_row, dtype=np.int32)
+        if cand_ptr.shape != (len(row_atom) + 1,) or (len(cand_ptr) and cand_ptr[-1] != len(cand)):
+            raise ValueError('cand_ptr must have one entry per row plus one and end at len(cand)')
+        s = self._torch.cuda.current_stream(self.device).cuda_stream
+        self.n_total = 0
+        self._L.check(self.lib.e3gnn_plist_set(
+            self._h, len(row_atom), len(atom_row), row_atom.ctypes.data_as(i32),
+            cand_ptr.ctypes.data_as(i64), cand.ctypes.data_as(i32), int(neighmask),
+            atom_row.ctypes.data_as(i32), s))
+        self.n_total = len(atom_row)
+
+    def __call__(self, x, cutoff):
+        import ctypes
+        torch, dev = self._torch, self.device
+        x = torch.as_tensor(x).to(dev, torch.float64).contiguous()
+        if self.n_total and x.shape != (self.n_total, 3):
+            raise ValueError('x must have one row per atom of the list (owned and ghost)')
+        ne = ctypes.c_int64()
+        s = torch.cuda.current_stream(dev).cuda_stream
+        self._L.check(self.lib.e3gnn_plist_build(self._h, x.data_ptr(), float(cutoff),
+                                                 ctypes.byref(ne), s))
+        E = ne.value
+        center = torch.empty(E, dtype=torch.int32, device=dev)
+        nbr = torch.empty(E, dtype=torch.int32, device=dev)
+        vec = torch.empty(E, 3, dtype=torch.float32, device=dev)
+        self._L.check(self.lib.e3gnn_plist_fetch(self._h, center.data_ptr(), nbr.data_ptr(),
+                                                 vec.data_ptr(), s))
+        # the fill pass reads x in stream order: keep it alive until then
+        x.record_stream(torch.cuda.current_stream(dev))
+        return center, nbr, vec

@@ -19,6 +19,8 @@ single all-reduce after each backward -- the same arithmetic as DDP's
 bucketed averaging (earlier, already-synchronised accumulation + the mean of
 the new contributions), one collective of 3.4 MB per backward.
 """
+import contextlib
+import gc
 import math
 import os
 
@@ -26,6 +28,26 @@ import numpy as np
 import torch
 
 from . import _keys as KEY
+
+
+@contextlib.contextmanager
+def _capturing(g, pool=None):
+    """``torch.cuda.graph(g, pool=pool)`` with the cyclic garbage collector
+    held off.  torch no longer collects before a capture, so a dead reference
+    cycle that owns a CUDAGraph (a dropped Trainer and its graphed step) could
+    be freed by a collection that happens to start inside the capture; the
+    graph's destructor then makes HIP calls that are illegal while a stream
+    captures, and the process aborts.  Collect first, then keep the collector
+    off until the capture has ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g, pool=pool):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 # config keys (sevenn/_keys.py:100-233)
 LOSS, LOSS_PARAM = 'loss', 'loss_param'
@@ -836,18 +858,18 @@ class GraphedRehearsalStep:
         torch.cuda.current_stream().wait_stream(side)
         if not tr.distributed:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _capturing(g):
                 loss, mloss = tr._rehearsal_body(sb, sm, graphs)
             return {'g': [g], 'b': sb, 'm': sm, 'graphs': graphs, 'out': (loss, mloss)}
         segs = [torch.cuda.CUDAGraph() for _ in range(3)]
-        with torch.cuda.graph(segs[0]):
+        with _capturing(segs[0]):
             tr.zero_grad()
             loss, _ = tr.loss_backward(sb, graphs[0], reduce=False)
         pool = segs[0].pool()
-        with torch.cuda.graph(segs[1], pool=pool):
+        with _capturing(segs[1], pool=pool):
             tr.optimizer.step()
             mloss, _ = tr.loss_backward(sm, graphs[1], reduce=False)
-        with torch.cuda.graph(segs[2], pool=pool):
+        with _capturing(segs[2], pool=pool):
             tr.optimizer.step()
         return {'g': segs, 'b': sb, 'm': sm, 'graphs': graphs,
                 'out': (loss.detach(), mloss.detach())}
