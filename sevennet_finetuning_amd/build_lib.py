@@ -20,7 +20,7 @@ OBJDIR = os.path.join(HERE, 'csrc', 'build')
 SOURCES = ['api.cpp', 'model_load.cpp', 'api_train.cpp', 'api_nlist.cpp', 'api_plist.cpp', 'api_d3.cpp', 'api_data.cpp',
            'collate.hip', 'generic.cpp',
            'gemm.hip', 'tp.hip', 'node.hip', 'fused.hip', 'neighbor.hip', 'd3.hip', 'train_ops.hip', 'gtp.hip', 'generic.hip', 'mlp_train.hip', 'tgemm.hip',
-           'fcn_train.hip', 'atom_virial.hip', 'segment_sum.hip', 'pairlist.hip']
+           'fcn_train.hip', 'atom_virial.hip', 'segment_sum.hip', 'pairlist.hip', 'scan.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', f'-I{INCLUDE}',
          '-Wall', '-Wno-unused-function']

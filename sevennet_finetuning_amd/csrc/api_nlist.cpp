@@ -12,6 +12,7 @@
 #include "api_util.h"
 #include "dbuf.h"
 #include "neighbor.h"
+#include "scan.h"
 
 using namespace e3gnn;
 
@@ -21,17 +22,17 @@ extern "C" {
 struct e3gnn_nlist {
   int device = 0;
   int64_t n = 0, E = 0;
-  NlGeom G{};
   const double* pos = nullptr;
   bool built = false;
   DBuf f0, bin, bin_count, bin_start, cursor, bin_atoms, deg, row_ptr, err;
+  DBuf bsum;  // the scans' block totals: scan_blocks(the longest array scanned) ints
   // rank graph (e3gnn_nlist_rank_build): counts and the row maps it keeps
   bool rank_built = false;
   int64_t n_local = 0, n_ghost = 0;
   int world = 0;
-  DBuf flag, fpos, centers, bflag, degrow, owned, gid, ghosts, lid, hist, hoff, recv, sc_sum,
-      sc_off;
-  // batch (e3gnn_nlist_batch_build): B structures, their geometries and row ranges
+  DBuf flag, fpos, centers, bflag, degrow, owned, gid, ghosts, lid, hist, hoff, recv;
+  // the structures of the last build (one, or the B of e3gnn_nlist_batch_build):
+  // geometries and row ranges, uploaded for a batch
   bool batch_built = false;
   int64_t B = 0;
   DBuf geoms, batch, aptr;
@@ -112,49 +113,135 @@ const char* nl_cluster_geom(NlGeom& G, const double* hp, int64_t n, double hgt[3
   return nullptr;
 }
 
-// The geometry of the box and the atoms binned (k_nl_bin, scan, k_nl_place):
-// the part e3gnn_nlist_build and e3gnn_nlist_rank_build share.  `all`: all
-// three dimensions periodic, else an isolated cluster.
-int nl_bin_atoms(e3gnn_nlist* h, int64_t n, const double* pos, const double* cell, bool all,
-                 double cutoff, hipStream_t s) {
+// What every build starts with: the handle reset, the geometry and the bins of
+// each of the B structures (rows [atom_ptr[k], atom_ptr[k + 1]); periodic[k]:
+// all three dimensions periodic with the cell at cells + 9 k, else an isolated
+// cluster), the workspace, and the atoms binned (bin, scan, place).  The single
+// and the rank build are B = 1, not `batched`: their kernels take the one
+// geometry by value, and nothing is uploaded.
+int nl_bin_atoms(e3gnn_nlist* h, bool batched, int64_t B, const int64_t* atom_ptr,
+                 const double* pos, const double* cells, const int32_t* periodic, double cutoff,
+                 hipStream_t s) {
   HIPCHK(hipSetDevice(h->device));
   h->built = false;
   h->rank_built = false;
   h->batch_built = false;
+  const int64_t n = atom_ptr[B];
   h->n = n;
+  h->B = B;
   h->pos = pos;
-  NlGeom& G = h->G;
-  G = NlGeom{};
-  G.rc2 = cutoff * cutoff;
-  G.periodic = all ? 1 : 0;
-  double hgt[3];
-  if (all) {
-    if (!cell) return fail(E3GNN_ERR_ARG, "null cell");
-    if (const char* why = nl_cell_geom(G, cell, hgt)) return fail(E3GNN_ERR_ARG, why);
-  } else {
-    std::vector<double> hp((size_t)n * 3);
+  // isolated members need their extent: one copy of the positions per build
+  std::vector<double> hp;
+  bool any_isolated = false;
+  for (int64_t k = 0; k < B; ++k) any_isolated |= periodic[k] == 0;
+  if (any_isolated) {
+    hp.resize((size_t)n * 3);
     if (n) HIPCHK(hipMemcpy(hp.data(), pos, hp.size() * 8, hipMemcpyDefault));
-    if (const char* why = nl_cluster_geom(G, hp.data(), n, hgt)) return fail(E3GNN_ERR_ARG, why);
   }
-  nl_bins(G, hgt, cutoff, n);
-  const int nbins = G.nb[0] * G.nb[1] * G.nb[2];
-  if (h->f0.ensure((size_t)std::max<int64_t>(n, 1) * 12) != hipSuccess ||
-      h->bin.ensure((size_t)std::max<int64_t>(n, 1) * 4) != hipSuccess ||
-      h->bin_atoms.ensure((size_t)std::max<int64_t>(n, 1) * 4) != hipSuccess ||
-      h->deg.ensure((size_t)std::max<int64_t>(n, 1) * 4) != hipSuccess ||
+  h->hgeoms.assign((size_t)B, NlGeomB{});
+  h->haptr.resize((size_t)B + 1);
+  int64_t nbins = 0;
+  for (int64_t k = 0; k < B; ++k) {
+    NlGeom& G = h->hgeoms[k].G;
+    const int64_t n_k = atom_ptr[k + 1] - atom_ptr[k];
+    G.rc2 = cutoff * cutoff;
+    G.periodic = periodic[k] ? 1 : 0;
+    double hgt[3];
+    const char* why = !periodic[k] ? nl_cluster_geom(G, hp.data() + 3 * atom_ptr[k], n_k, hgt)
+                      : !cells     ? "null cell"
+                                   : nl_cell_geom(G, cells + 9 * k, hgt);
+    if (why)
+      return fail(E3GNN_ERR_ARG,
+                  (batched ? "batch: structure " + std::to_string(k) + ": " : std::string()) + why);
+    nl_bins(G, hgt, cutoff, n_k);
+    h->hgeoms[k].bin_base = (int)nbins;
+    h->haptr[k] = (int32_t)atom_ptr[k];
+    nbins += (int64_t)G.nb[0] * G.nb[1] * G.nb[2];
+    if (nbins >= (int64_t)1 << 31) return fail(E3GNN_ERR_ARG, "batch: bin count exceeds int32");
+  }
+  h->haptr[B] = (int32_t)n;
+  const size_t n1 = (size_t)std::max<int64_t>(n, 1);
+  if (h->f0.ensure(n1 * 12) != hipSuccess || h->bin.ensure(n1 * 4) != hipSuccess ||
+      h->bin_atoms.ensure(n1 * 4) != hipSuccess || h->deg.ensure(n1 * 4) != hipSuccess ||
       h->row_ptr.ensure((size_t)(n + 1) * 4) != hipSuccess ||
       h->bin_count.ensure((size_t)nbins * 4) != hipSuccess ||
       h->bin_start.ensure((size_t)(nbins + 1) * 4) != hipSuccess ||
-      h->cursor.ensure((size_t)nbins * 4) != hipSuccess || h->err.ensure(4) != hipSuccess)
+      h->cursor.ensure((size_t)nbins * 4) != hipSuccess || h->err.ensure(16) != hipSuccess ||
+      h->bsum.ensure((size_t)scan_blocks((int)std::max(n, nbins)) * 4) != hipSuccess ||
+      (batched && (h->geoms.ensure((size_t)B * sizeof(NlGeomB)) != hipSuccess ||
+                   h->batch.ensure(n1 * 4) != hipSuccess ||
+                   h->aptr.ensure((size_t)(B + 1) * 4) != hipSuccess)))
     return fail(E3GNN_ERR_HIP, "neighbour-list workspace allocation failed");
   int* err = h->err.i();
-  HIPCHK(hipMemsetAsync(err, 0, 4, s));
+  HIPCHK(hipMemsetAsync(err, 0, 16, s));
   HIPCHK(hipMemsetAsync(h->bin_count.p, 0, (size_t)nbins * 4, s));
   HIPCHK(hipMemsetAsync(h->cursor.p, 0, (size_t)nbins * 4, s));
-  HIPCHK(launch_nl_bin((int)n, pos, G, h->f0.i(), h->bin.i(), h->bin_count.i(), err, s));
-  HIPCHK(launch_nl_scan(nbins, h->bin_count.i(), h->bin_start.i(), s));
+  if (batched) {
+    HIPCHK(hipMemcpyAsync(h->geoms.p, h->hgeoms.data(), (size_t)B * sizeof(NlGeomB),
+                          hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->aptr.p, h->haptr.data(), (size_t)(B + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(launch_nlb_batch((int)B, h->aptr.i(), h->batch.i(), s));
+    HIPCHK(launch_nlb_bin((int)n, pos, (const NlGeomB*)h->geoms.p, h->batch.i(), h->f0.i(),
+                          h->bin.i(), h->bin_count.i(), err, s));
+  } else {
+    HIPCHK(launch_nl_bin((int)n, pos, h->hgeoms[0].G, h->f0.i(), h->bin.i(), h->bin_count.i(), err,
+                         s));
+  }
+  HIPCHK(launch_exclusive_scan((int)nbins, h->bin_count.i(), h->bin_start.i(), h->bsum.i(), s));
   HIPCHK(launch_nl_place((int)n, h->bin.i(), h->bin_start.i(), h->cursor.i(), h->bin_atoms.i(), s));
   return E3GNN_OK;
+}
+
+// The fetched err words of a build or a fetch (neighbor.h: int[1], of a batch
+// int[4]) as its refusal, or E3GNN_OK.
+int nl_refusal(const int* herr, bool batched) {
+  auto where = [&](int slot) {
+    return batched ? "batch: structure " + std::to_string(herr[slot] - 1) + ": " : std::string();
+  };
+  if (herr[0] & 1)
+    return fail(E3GNN_ERR_ARG, where(1) + "non-finite or out-of-box atom position");
+  if (herr[0] & 8)
+    return fail(E3GNN_ERR_GRAPH, "rank graph: an owner value is outside [0, world)");
+  if (herr[0] & 4)
+    return fail(E3GNN_ERR_GRAPH, where(3) + "a centre has more than " + std::to_string(NL_MAXD) +
+                                     " neighbours (device neighbour-list limit)");
+  if (herr[0] & 2)
+    return fail(E3GNN_ERR_GRAPH, where(2) + "periodic image shift beyond +-1024 cells");
+  return E3GNN_OK;
+}
+
+// The single and the batched build after the binning: the count pass, the
+// degrees scanned into row_ptr, the device's refusals, the edge count.
+int nl_count_edges(e3gnn_nlist* h, bool batched, int64_t* n_edges, hipStream_t s) {
+  const int n = (int)h->n;
+  int* err = h->err.i();
+  if (batched)
+    HIPCHK(launch_nlb_search(false, n, h->pos, (const NlGeomB*)h->geoms.p, h->batch.i(),
+                             h->f0.i(), h->bin.i(), h->bin_start.i(), h->bin_atoms.i(), h->deg.i(),
+                             nullptr, nullptr, nullptr, nullptr, nullptr, err, s));
+  else
+    HIPCHK(launch_nl_search(false, n, h->pos, h->hgeoms[0].G, h->f0.i(), h->bin.i(),
+                            h->bin_start.i(), h->bin_atoms.i(), h->deg.i(), nullptr, nullptr,
+                            nullptr, nullptr, nullptr, err, s));
+  HIPCHK(launch_exclusive_scan(n, h->deg.i(), h->row_ptr.i(), h->bsum.i(), s));
+  int herr[4] = {0, 0, 0, 0}, total = 0;
+  HIPCHK(hipMemcpyAsync(herr, err, batched ? 16 : 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&total, h->row_ptr.i() + n, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (const int rc = nl_refusal(herr, batched)) return rc;
+  if (total < 0) return fail(E3GNN_ERR_GRAPH, "edge count exceeds int32");
+  h->E = total;
+  (batched ? h->batch_built : h->built) = true;
+  if (n_edges) *n_edges = total;
+  return E3GNN_OK;
+}
+
+// The refusal of a fill pass (a shift beyond the key's range), once it has run.
+int nl_fill_refusal(e3gnn_nlist* h, bool batched, hipStream_t s) {
+  int herr[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(herr, h->err.i(), batched ? 16 : 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return nl_refusal(herr, batched);
 }
 }  // namespace
 
@@ -169,26 +256,10 @@ int e3gnn_nlist_build(e3gnn_nlist* h, int64_t n, const double* pos, const double
   if (!all && !none)
     return fail(E3GNN_ERR_ARG, "device neighbour list: pbc must be all true or all false");
   hipStream_t s = (hipStream_t)stream;
-  if (const int rc = nl_bin_atoms(h, n, pos, cell, all, cutoff, s)) return rc;
-  const NlGeom& G = h->G;
-  int* err = h->err.i();
-  HIPCHK(launch_nl_search(false, (int)n, pos, G, h->f0.i(), h->bin.i(), h->bin_start.i(),
-                          h->bin_atoms.i(), h->deg.i(), nullptr, nullptr, nullptr, nullptr, nullptr,
-                          err, s));
-  if (n > 0) HIPCHK(launch_nl_scan((int)n, h->deg.i(), h->row_ptr.i(), s));
-  int herr = 0, total = 0;
-  HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
-  if (n > 0) HIPCHK(hipMemcpyAsync(&total, h->row_ptr.i() + n, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (herr & 1) return fail(E3GNN_ERR_ARG, "non-finite or out-of-box atom position");
-  if (herr & 4)
-    return fail(E3GNN_ERR_GRAPH, "a centre has more than " + std::to_string(NL_MAXD) +
-                                     " neighbours (device neighbour-list limit)");
-  if (total < 0) return fail(E3GNN_ERR_GRAPH, "edge count exceeds int32");
-  h->E = total;
-  h->built = true;
-  if (n_edges) *n_edges = total;
-  return E3GNN_OK;
+  const int64_t atom_ptr[2] = {0, n};
+  const int32_t periodic = all ? 7 : 0;
+  if (const int rc = nl_bin_atoms(h, false, 1, atom_ptr, pos, cell, &periodic, cutoff, s)) return rc;
+  return nl_count_edges(h, false, n_edges, s);
 }
 
 int e3gnn_nlist_fetch(e3gnn_nlist* h, int32_t* center, int32_t* nbr, int32_t* shift, float* vec,
@@ -199,14 +270,10 @@ int e3gnn_nlist_fetch(e3gnn_nlist* h, int32_t* center, int32_t* nbr, int32_t* sh
   hipStream_t s = (hipStream_t)stream;
   int* err = h->err.i();
   HIPCHK(hipMemsetAsync(err, 0, 4, s));
-  HIPCHK(launch_nl_search(true, (int)h->n, h->pos, h->G, h->f0.i(), h->bin.i(), h->bin_start.i(),
-                          h->bin_atoms.i(), nullptr, h->row_ptr.i(), center, nbr, shift, vec, err,
-                          s));
-  int herr = 0;
-  HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (herr & 2) return fail(E3GNN_ERR_GRAPH, "periodic image shift beyond +-1024 cells");
-  return E3GNN_OK;
+  HIPCHK(launch_nl_search(true, (int)h->n, h->pos, h->hgeoms[0].G, h->f0.i(), h->bin.i(),
+                          h->bin_start.i(), h->bin_atoms.i(), nullptr, h->row_ptr.i(), center, nbr,
+                          shift, vec, err, s));
+  return nl_fill_refusal(h, false, s);
 }
 
 namespace {
@@ -234,18 +301,18 @@ int e3gnn_nlist_rank_build(e3gnn_nlist* h, int64_t n, const double* pos, const d
   if (const char* why = nl_rank_args(h != nullptr, n, pos, cell, cutoff, owner, rank, world))
     return fail(E3GNN_ERR_ARG, why);
   hipStream_t s = (hipStream_t)stream;
-  if (const int rc = nl_bin_atoms(h, n, pos, cell, true, cutoff, s)) return rc;
-  const NlGeom& G = h->G;
+  const int64_t atom_ptr[2] = {0, n};
+  const int32_t periodic = 7;
+  if (const int rc = nl_bin_atoms(h, false, 1, atom_ptr, pos, cell, &periodic, cutoff, s)) return rc;
+  const NlGeom& G = h->hgeoms[0].G;
   int* err = h->err.i();
   const size_t n1 = (size_t)std::max<int64_t>(n, 1);
   if (h->flag.ensure(n1 * 4) != hipSuccess || h->fpos.ensure((n1 + 1) * 4) != hipSuccess ||
-      h->lid.ensure(n1 * 4) != hipSuccess || h->recv.ensure((size_t)world * 8) != hipSuccess ||
-      h->sc_sum.ensure((size_t)nl_scan_blocks((int)n) * 4) != hipSuccess ||
-      h->sc_off.ensure(((size_t)nl_scan_blocks((int)n) + 1) * 4) != hipSuccess)
+      h->lid.ensure(n1 * 4) != hipSuccess || h->recv.ensure((size_t)world * 8) != hipSuccess)
     return fail(E3GNN_ERR_HIP, "rank-graph workspace allocation failed");
-  // the scans run over many workgroups (per-atom arrays; workspaces sized above and below)
+  // bsum: sized for n entries by nl_bin_atoms, and for the ghost histogram below
   auto scan = [&](int m, const int* cnt, int* out) {
-    return launch_rk_scan(m, cnt, out, h->sc_sum.i(), h->sc_off.i(), s);
+    return launch_exclusive_scan(m, cnt, out, h->bsum.i(), s);
   };
   // the rank's atoms in id order
   HIPCHK(launch_rk_mark((int)n, owner, rank, world, h->flag.i(), err, s));
@@ -254,8 +321,7 @@ int e3gnn_nlist_rank_build(e3gnn_nlist* h, int64_t n, const double* pos, const d
   HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(&nc, h->fpos.i() + n, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  if (herr & 1) return fail(E3GNN_ERR_ARG, "non-finite or out-of-box atom position");
-  if (herr & 8) return fail(E3GNN_ERR_GRAPH, "rank graph: an owner value is outside [0, world)");
+  if (const int rc = nl_refusal(&herr, false)) return rc;
   const size_t nc1 = (size_t)std::max(nc, 1);
   if (h->centers.ensure(nc1 * 4) != hipSuccess || h->bflag.ensure(nc1 * 4) != hipSuccess ||
       h->degrow.ensure(nc1 * 4) != hipSuccess || h->owned.ensure(nc1 * 4) != hipSuccess ||
@@ -288,17 +354,14 @@ int e3gnn_nlist_rank_build(e3gnn_nlist* h, int64_t n, const double* pos, const d
   HIPCHK(hipMemcpyAsync(&ng, h->fpos.i() + n, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  if (herr & 4)
-    return fail(E3GNN_ERR_GRAPH, "a centre has more than " + std::to_string(NL_MAXD) +
-                                     " neighbours (device neighbour-list limit)");
+  if (const int rc = nl_refusal(&herr, false)) return rc;
   if (total < 0) return fail(E3GNN_ERR_GRAPH, "edge count exceeds int32");
   // ghosts by (owner, id): stable counting sort over blocks of 256
   const int nblk = std::max(1, (ng + 255) / 256);
   const size_t nh = (size_t)world * nblk;
   if (h->ghosts.ensure((size_t)std::max(ng, 1) * 4) != hipSuccess ||
       h->hist.ensure(nh * 4) != hipSuccess || h->hoff.ensure((nh + 1) * 4) != hipSuccess ||
-      h->sc_sum.ensure((size_t)nl_scan_blocks((int)nh) * 4) != hipSuccess ||
-      h->sc_off.ensure(((size_t)nl_scan_blocks((int)nh) + 1) * 4) != hipSuccess)
+      h->bsum.ensure((size_t)scan_blocks((int)nh) * 4) != hipSuccess)
     return fail(E3GNN_ERR_HIP, "rank-graph workspace allocation failed");
   HIPCHK(launch_rk_ghost_sort(false, ng, world, nblk, h->gid.i(), owner, h->hist.i(), nullptr, nc,
                               nullptr, nullptr, s));
@@ -339,14 +402,10 @@ int e3gnn_nlist_rank_fetch(e3gnn_nlist* h, int32_t* owned, int32_t* ghosts, int6
   NlRank rk{};
   rk.centers = h->owned.i();
   rk.lid = h->lid.i();
-  HIPCHK(launch_nl_rank_search(true, (int)h->n_local, h->pos, h->G, h->f0.i(), h->bin.i(),
+  HIPCHK(launch_nl_rank_search(true, (int)h->n_local, h->pos, h->hgeoms[0].G, h->f0.i(), h->bin.i(),
                                h->bin_start.i(), h->bin_atoms.i(), nullptr, h->row_ptr.i(),
                                edge_center, edge_nbr, shift, edge_vec, err, rk, s));
-  int herr = 0;
-  HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (herr & 2) return fail(E3GNN_ERR_GRAPH, "periodic image shift beyond +-1024 cells");
-  return E3GNN_OK;
+  return nl_fill_refusal(h, false, s);
 }
 
 // ------------------------------------------------------------------- batch
@@ -383,85 +442,9 @@ int e3gnn_nlist_batch_build(e3gnn_nlist* h, int64_t B, const int64_t* atom_ptr, 
     const std::string why = nl_batch_args(h != nullptr, B, atom_ptr, pos, cells, periodic, cutoff);
     if (!why.empty()) return fail(E3GNN_ERR_ARG, why);
   }
-  HIPCHK(hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
-  h->built = false;
-  h->rank_built = false;
-  h->batch_built = false;
-  const int64_t n = atom_ptr[B];
-  h->n = n;
-  h->B = B;
-  h->pos = pos;
-  // the geometries, as nl_bin_atoms computes the one of a single structure;
-  // isolated members need their extent: one copy of the positions per batch
-  std::vector<double> hp;
-  bool any_isolated = false;
-  for (int64_t k = 0; k < B; ++k) any_isolated |= periodic[k] == 0;
-  if (any_isolated) {
-    hp.resize((size_t)n * 3);
-    HIPCHK(hipMemcpy(hp.data(), pos, hp.size() * 8, hipMemcpyDefault));
-  }
-  h->hgeoms.assign((size_t)B, NlGeomB{});
-  h->haptr.resize((size_t)B + 1);
-  int64_t nbins = 0;
-  for (int64_t k = 0; k < B; ++k) {
-    NlGeom& G = h->hgeoms[k].G;
-    const int64_t n_k = atom_ptr[k + 1] - atom_ptr[k];
-    G.rc2 = cutoff * cutoff;
-    G.periodic = periodic[k] ? 1 : 0;
-    double hgt[3];
-    const char* why = periodic[k] ? nl_cell_geom(G, cells + 9 * k, hgt)
-                                  : nl_cluster_geom(G, hp.data() + 3 * atom_ptr[k], n_k, hgt);
-    if (why) return fail(E3GNN_ERR_ARG, "batch: structure " + std::to_string(k) + ": " + why);
-    nl_bins(G, hgt, cutoff, n_k);
-    h->hgeoms[k].bin_base = (int)nbins;
-    h->haptr[k] = (int32_t)atom_ptr[k];
-    nbins += (int64_t)G.nb[0] * G.nb[1] * G.nb[2];
-    if (nbins >= (int64_t)1 << 31) return fail(E3GNN_ERR_ARG, "batch: bin count exceeds int32");
-  }
-  h->haptr[B] = (int32_t)n;
-  if (h->f0.ensure((size_t)n * 12) != hipSuccess || h->bin.ensure((size_t)n * 4) != hipSuccess ||
-      h->bin_atoms.ensure((size_t)n * 4) != hipSuccess || h->deg.ensure((size_t)n * 4) != hipSuccess ||
-      h->row_ptr.ensure((size_t)(n + 1) * 4) != hipSuccess ||
-      h->bin_count.ensure((size_t)nbins * 4) != hipSuccess ||
-      h->bin_start.ensure((size_t)(nbins + 1) * 4) != hipSuccess ||
-      h->cursor.ensure((size_t)nbins * 4) != hipSuccess || h->err.ensure(16) != hipSuccess ||
-      h->geoms.ensure((size_t)B * sizeof(NlGeomB)) != hipSuccess ||
-      h->batch.ensure((size_t)n * 4) != hipSuccess || h->aptr.ensure((size_t)(B + 1) * 4) != hipSuccess)
-    return fail(E3GNN_ERR_HIP, "neighbour-list workspace allocation failed");
-  int* err = h->err.i();
-  const NlGeomB* geoms = (const NlGeomB*)h->geoms.p;
-  HIPCHK(hipMemcpyAsync(h->geoms.p, h->hgeoms.data(), (size_t)B * sizeof(NlGeomB),
-                        hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(h->aptr.p, h->haptr.data(), (size_t)(B + 1) * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(err, 0, 16, s));
-  HIPCHK(hipMemsetAsync(h->bin_count.p, 0, (size_t)nbins * 4, s));
-  HIPCHK(hipMemsetAsync(h->cursor.p, 0, (size_t)nbins * 4, s));
-  HIPCHK(launch_nlb_batch((int)B, h->aptr.i(), h->batch.i(), s));
-  HIPCHK(launch_nlb_bin((int)n, pos, geoms, h->batch.i(), h->f0.i(), h->bin.i(), h->bin_count.i(),
-                        err, s));
-  HIPCHK(launch_nl_scan((int)nbins, h->bin_count.i(), h->bin_start.i(), s));
-  HIPCHK(launch_nl_place((int)n, h->bin.i(), h->bin_start.i(), h->cursor.i(), h->bin_atoms.i(), s));
-  HIPCHK(launch_nlb_search(false, (int)n, pos, geoms, h->batch.i(), h->f0.i(), h->bin.i(),
-                           h->bin_start.i(), h->bin_atoms.i(), h->deg.i(), nullptr, nullptr, nullptr,
-                           nullptr, nullptr, err, s));
-  HIPCHK(launch_nl_scan((int)n, h->deg.i(), h->row_ptr.i(), s));
-  int herr[4] = {0, 0, 0, 0}, total = 0;
-  HIPCHK(hipMemcpyAsync(herr, err, 16, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&total, h->row_ptr.i() + n, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (herr[0] & 1)
-    return fail(E3GNN_ERR_ARG, "batch: structure " + std::to_string(herr[1] - 1) +
-                                   ": non-finite or out-of-box atom position");
-  if (herr[0] & 4)
-    return fail(E3GNN_ERR_GRAPH, "batch: structure " + std::to_string(herr[3] - 1) +
-                                     ": a centre has more than " + std::to_string(NL_MAXD) +
-                                     " neighbours (device neighbour-list limit)");
-  if (total < 0) return fail(E3GNN_ERR_GRAPH, "edge count exceeds int32");
-  h->E = total;
-  h->batch_built = true;
-  if (n_edges) *n_edges = total;
-  return E3GNN_OK;
+  if (const int rc = nl_bin_atoms(h, true, B, atom_ptr, pos, cells, periodic, cutoff, s)) return rc;
+  return nl_count_edges(h, true, n_edges, s);
 }
 
 int e3gnn_nlist_batch_fetch(e3gnn_nlist* h, int32_t* edge_center, int32_t* edge_nbr, int32_t* shift,
@@ -476,13 +459,7 @@ int e3gnn_nlist_batch_fetch(e3gnn_nlist* h, int32_t* edge_center, int32_t* edge_
                            h->f0.i(), h->bin.i(), h->bin_start.i(), h->bin_atoms.i(), nullptr,
                            h->row_ptr.i(), edge_center, edge_nbr, shift, edge_vec, err, s));
   if (edge_ptr) HIPCHK(launch_nlb_edge_ptr((int)h->B, h->aptr.i(), h->row_ptr.i(), edge_ptr, s));
-  int herr[4] = {0, 0, 0, 0};
-  HIPCHK(hipMemcpyAsync(herr, err, 16, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (herr[0] & 2)
-    return fail(E3GNN_ERR_GRAPH, "batch: structure " + std::to_string(herr[2] - 1) +
-                                     ": periodic image shift beyond +-1024 cells");
-  return E3GNN_OK;
+  return nl_fill_refusal(h, true, s);
 }
 
 }  // extern "C"

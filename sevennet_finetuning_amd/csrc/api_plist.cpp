@@ -1,5 +1,5 @@
 // The cutoff filter over a host code's neighbour list behind the C ABI
-// (include/e3gnn.h, e3gnn_plist_*; kernel in pairlist.hip, scan in neighbor.hip).
+// (include/e3gnn.h, e3gnn_plist_*; kernel in pairlist.hip, scan in scan.hip).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -11,8 +11,8 @@
 #include "../../include/e3gnn.h"
 #include "api_util.h"
 #include "dbuf.h"
-#include "neighbor.h"
 #include "pairlist.h"
+#include "scan.h"
 
 using namespace e3gnn;
 
@@ -25,7 +25,7 @@ struct e3gnn_plist {
   bool is_set = false, built = false;
   const double* x = nullptr;   // of the last build (the fill pass reads it again)
   double rc2 = 0.0;
-  DBuf row_atom, cand_ptr, cand, atom_row, deg, row_ptr, sc_sum, sc_off;
+  DBuf row_atom, cand_ptr, cand, atom_row, deg, row_ptr, bsum;
   void* stage = nullptr;       // pinned host image of the four uploads
   size_t stage_cap = 0;
   ~e3gnn_plist() {
@@ -136,12 +136,10 @@ int e3gnn_plist_set(e3gnn_plist* h, int64_t n, int64_t n_total, const int32_t* r
   std::memcpy(st, cand_ptr, b_ptr);
   std::memcpy(st + b_ptr + b_cand, row_atom, b_row);
   std::memcpy(st + b_ptr + b_cand + b_row, atom_row, b_atom);
-  const int nblk = nl_scan_blocks((int)n);
   if (h->cand_ptr.ensure(b_ptr) != hipSuccess || h->cand.ensure(b_cand) != hipSuccess ||
       h->row_atom.ensure(b_row) != hipSuccess || h->atom_row.ensure(b_atom) != hipSuccess ||
       h->deg.ensure(b_row) != hipSuccess || h->row_ptr.ensure((size_t)(n + 1) * 4) != hipSuccess ||
-      h->sc_sum.ensure((size_t)nblk * 4) != hipSuccess ||
-      h->sc_off.ensure(((size_t)nblk + 1) * 4) != hipSuccess)
+      h->bsum.ensure((size_t)scan_blocks((int)n) * 4) != hipSuccess)
     return fail(E3GNN_ERR_HIP, "list-filter workspace allocation failed");
   HIPCHK(hipMemcpyAsync(h->cand_ptr.p, st, b_ptr, hipMemcpyHostToDevice, s));
   if (b_cand) HIPCHK(hipMemcpyAsync(h->cand.p, st_cand, b_cand, hipMemcpyHostToDevice, s));
@@ -172,7 +170,7 @@ int e3gnn_plist_build(e3gnn_plist* h, const double* x, double cutoff, int64_t* n
   HIPCHK(launch_pl_filter(false, n, x, h->row_atom.i(), (const int64_t*)h->cand_ptr.p, h->cand.i(),
                           h->neighmask, h->atom_row.i(), h->rc2, h->deg.i(), nullptr, nullptr,
                           nullptr, nullptr, s));
-  HIPCHK(launch_rk_scan(n, h->deg.i(), h->row_ptr.i(), h->sc_sum.i(), h->sc_off.i(), s));
+  HIPCHK(launch_exclusive_scan(n, h->deg.i(), h->row_ptr.i(), h->bsum.i(), s));
   int total = 0;
   HIPCHK(hipMemcpyAsync(&total, h->row_ptr.i() + n, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));

@@ -1,4 +1,4 @@
-// Launchers of neighbor.hip (device cell-list neighbour list).
+// Launchers of neighbor.hip (device cell-list neighbour list; its scans: scan.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -33,7 +33,6 @@ hipError_t launch_nl_bin(int n, const double* pos, const NlGeom& G, int* f0, int
                          int* bin_count, int* err, hipStream_t s);
 hipError_t launch_nl_place(int n, const int* bin, const int* bin_start, int* cursor,
                            int* bin_atoms, hipStream_t s);
-hipError_t launch_nl_scan(int n, const int* cnt, int* out, hipStream_t s);
 hipError_t launch_nl_search(bool fill, int n, const double* pos, const NlGeom& G, const int* f0,
                             const int* bin, const int* bin_start, const int* bin_atoms, int* deg,
                             const int* row_ptr, int* center, int* nbr, int* shift, float* vec,
@@ -44,10 +43,6 @@ hipError_t launch_nl_rank_search(bool fill, int nc, const double* pos, const NlG
                                  const int* bin_atoms, int* deg, const int* row_ptr, int* center,
                                  int* nbr, int* shift, float* vec, int* err, const NlRank& rk,
                                  hipStream_t s);
-// exclusive scan of cnt[0..n) into out[0..n] over many workgroups; workspaces
-// bsum [nl_scan_blocks(n)], boff [nl_scan_blocks(n) + 1]
-int nl_scan_blocks(int n);
-hipError_t launch_rk_scan(int n, const int* cnt, int* out, int* bsum, int* boff, hipStream_t s);
 // mine[a] = (owner[a] == rank); err |= 8 for an owner outside [0, world)
 hipError_t launch_rk_mark(int n, const int* owner, int rank, int world, int* mine, int* err,
                           hipStream_t s);

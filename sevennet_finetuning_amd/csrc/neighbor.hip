@@ -18,8 +18,10 @@
 // the CSR offsets, pass 2 recomputes the hits into LDS, sorts the centre's keys
 // (j, Sx, Sy, Sz) with a bitonic network and writes them: deterministic.
 //
-// The batched form (k_nlb_*, at the end) runs the same passes over many
-// structures concatenated, each with its own geometry and bins.
+// The binning (nl_bin) and the search (nl_search) exist once.  The single and
+// the rank build pass their one geometry as a kernel argument (k_nl_*); the
+// batched form (k_nlb_*) runs the same bodies over many structures
+// concatenated, each with its own geometry and bins (see "batch" below).
 #include "neighbor.h"
 
 #pragma clang fp contract(off)
@@ -27,14 +29,25 @@
 namespace e3gnn {
 namespace {
 
+// err is int[1] (single and rank build) or int[4] (BATCH: the flags and, for
+// bit 1, 2, 4, 1 + the largest offending structure index in err[1], [2], [3])
+template <bool BATCH>
+__device__ __forceinline__ void nl_flag(int* __restrict__ err, int bit, int st) {
+  atomicOr(err, bit);
+  if constexpr (BATCH) atomicMax(err + (bit == 1 ? 1 : bit == 2 ? 2 : 3), st + 1);
+}
+
 // ---------------------------------------------------------------- binning
-__global__ void k_nl_bin(int n, const double* __restrict__ pos, NlGeom G, int* __restrict__ f0,
-                         int* __restrict__ bin, int* __restrict__ bin_count, int* __restrict__ err) {
-  const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= n) return;
+// atom a of structure st (geometry G, first bin bin_base): f0 = floor of its
+// fractional coordinates, bin = the bin of the wrapped remainder
+template <bool BATCH>
+__device__ __forceinline__ void nl_bin(int a, const double* __restrict__ pos, const NlGeom& G,
+                                       int bin_base, int st, int* __restrict__ f0,
+                                       int* __restrict__ bin, int* __restrict__ bin_count,
+                                       int* __restrict__ err) {
   const double p0 = pos[3 * a] - G.origin[0], p1 = pos[3 * a + 1] - G.origin[1],
                p2 = pos[3 * a + 2] - G.origin[2];
-  int b[3];
+  int b[3], fl3[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const double f = ((p0 * G.inv[k]) + (p1 * G.inv[3 + k])) + (p2 * G.inv[6 + k]);
@@ -43,13 +56,28 @@ __global__ void k_nl_bin(int n, const double* __restrict__ pos, NlGeom G, int* _
     int bk = (int)(fw * G.nb[k]);
     bk = bk < 0 ? 0 : (bk >= G.nb[k] ? G.nb[k] - 1 : bk);
     b[k] = bk;
-    if (!(fl > -1e9 && fl < 1e9)) atomicOr(err, 1);  // non-finite or absurd position
-    f0[3 * a + k] = (int)fl;
+    if (!(fl > -1e9 && fl < 1e9)) nl_flag<BATCH>(err, 1, st);  // non-finite or absurd position
+    fl3[k] = (int)fl;
+    f0[3 * a + k] = fl3[k];
   }
-  if (!G.periodic && (f0[3 * a] | f0[3 * a + 1] | f0[3 * a + 2])) atomicOr(err, 1);
-  const int id = (b[0] * G.nb[1] + b[1]) * G.nb[2] + b[2];
+  if (!G.periodic && (fl3[0] | fl3[1] | fl3[2])) nl_flag<BATCH>(err, 1, st);
+  const int id = bin_base + ((b[0] * G.nb[1] + b[1]) * G.nb[2] + b[2]);
   bin[a] = id;
   atomicAdd(&bin_count[id], 1);
+}
+__global__ void k_nl_bin(int n, const double* __restrict__ pos, NlGeom G, int* __restrict__ f0,
+                         int* __restrict__ bin, int* __restrict__ bin_count, int* __restrict__ err) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a < n) nl_bin<false>(a, pos, G, 0, 0, f0, bin, bin_count, err);
+}
+__global__ void k_nlb_bin(int n, const double* __restrict__ pos,
+                          const NlGeomB* __restrict__ geoms, const int* __restrict__ batch,
+                          int* __restrict__ f0, int* __restrict__ bin,
+                          int* __restrict__ bin_count, int* __restrict__ err) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= n) return;
+  const int st = batch[a];
+  nl_bin<true>(a, pos, geoms[st].G, geoms[st].bin_base, st, f0, bin, bin_count, err);
 }
 
 __global__ void k_nl_place(int n, const int* __restrict__ bin, const int* __restrict__ bin_start,
@@ -58,31 +86,6 @@ __global__ void k_nl_place(int n, const int* __restrict__ bin, const int* __rest
   if (a >= n) return;
   const int id = bin[a];
   bin_atoms[bin_start[id] + atomicAdd(&cursor[id], 1)] = a;
-}
-
-// exclusive scan of cnt[0..n) into out[0..n] (out[n] = total), one workgroup
-__global__ __launch_bounds__(1024) void k_nl_scan(int n, const int* __restrict__ cnt,
-                                                  int* __restrict__ out) {
-  __shared__ long long part[1024];
-  const int t = threadIdx.x;
-  const int chunk = (n + 1023) / 1024;
-  const int b = t * chunk, e = min(b + chunk, n);
-  long long s = 0;
-  for (int i = b; i < e; ++i) s += cnt[i];
-  part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {  // Hillis-Steele inclusive scan
-    const long long v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  long long run = part[t] - s;
-  for (int i = b; i < e; ++i) {
-    out[i] = (int)run;
-    run += cnt[i];
-  }
-  if (t == 1023) out[n] = (int)part[1023];
 }
 
 // ---------------------------------------------------------------- search
@@ -115,20 +118,22 @@ __device__ __forceinline__ Hit nl_vec(const double* __restrict__ pos, const NlGe
 // ids, the count pass also flags boundary centres and ghost atoms, and the fill
 // pass writes local rows (the centre's position in the list, lid[j]) while the
 // keys still sort by the global (j, S).
-template <bool FILL, bool RANK>
-__global__ __launch_bounds__(256) void k_nl_search(
-    int n, const double* __restrict__ pos, NlGeom G, const int* __restrict__ f0,
+// BATCH = true is the batched form: centre ci belongs to structure st, whose
+// geometry is G and whose bins start at bin_base; rows, bins and keys are those
+// of the concatenated batch, so a structure's edges come out in the single
+// build's order with its first row added to i and j.
+// K: the wave's NL_MAXD sort keys in LDS.
+template <bool FILL, bool RANK, bool BATCH>
+__device__ __forceinline__ void nl_search(
+    int ci, const double* __restrict__ pos, const NlGeom& G, int bin_base, int st,
+    unsigned long long* __restrict__ K, const int* __restrict__ f0,
     const int* __restrict__ bin, const int* __restrict__ bin_start,
     const int* __restrict__ bin_atoms, int* __restrict__ deg, const int* __restrict__ row_ptr,
     int* __restrict__ center, int* __restrict__ nbr, int* __restrict__ shift,
-    float* __restrict__ vec, int* __restrict__ err, NlRank rk) {
-  __shared__ unsigned long long keys[4][NL_MAXD];
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ci = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wid);
-  if (ci >= n) return;
+    float* __restrict__ vec, int* __restrict__ err, const NlRank& rk) {
+  const int lane = threadIdx.x & 63;
   const int i = RANK ? __builtin_amdgcn_readfirstlane(rk.centers[ci]) : ci;
-  unsigned long long* K = keys[wid];
-  const int bi = bin[i];
+  const int bi = bin[i] - bin_base;
   const int b[3] = {bi / (G.nb[1] * G.nb[2]), (bi / G.nb[2]) % G.nb[1], bi % G.nb[2]};
   const int fi[3] = {f0[3 * i], f0[3 * i + 1], f0[3 * i + 2]};
   const double rc2 = G.rc2;
@@ -153,7 +158,7 @@ __global__ __launch_bounds__(256) void k_nl_search(
           }
         }
         if (skip) continue;
-        const int id = (c[0] * G.nb[1] + c[1]) * G.nb[2] + c[2];
+        const int id = bin_base + ((c[0] * G.nb[1] + c[1]) * G.nb[2] + c[2]);
         const int s = bin_start[id], e = bin_start[id + 1];
         for (int t0 = s; t0 < e; t0 += 64) {
           const int t = t0 + lane;
@@ -178,10 +183,13 @@ __global__ __launch_bounds__(256) void k_nl_search(
             const int slot = count + __popcll(m & ((1ull << lane) - 1));
             const int lim = 1 << SB;
             if (S[0] < -lim || S[0] >= lim || S[1] < -lim || S[1] >= lim || S[2] < -lim ||
-                S[2] >= lim)
-              atomicOr(err, 2);
-            else if (slot < NL_MAXD)
-              K[slot] = nl_key(j, S[0], S[1], S[2]);
+                S[2] >= lim) {
+              // the call fails, but the sort and the write-out below still decode
+              // this slot: give it a key they can index with (this j, no shift)
+              nl_flag<BATCH>(err, 2, st);
+              S[0] = S[1] = S[2] = 0;
+            }
+            if (slot < NL_MAXD) K[slot] = nl_key(j, S[0], S[1], S[2]);
           }
           count += __popcll(m);
         }
@@ -190,7 +198,7 @@ __global__ __launch_bounds__(256) void k_nl_search(
     if (lane == 0) {
       deg[ci] = count;
       if constexpr (RANK) rk.boundary_flag[ci] = boundary ? 1 : 0;
-      if (count > NL_MAXD) atomicOr(err, 4);
+      if (count > NL_MAXD) nl_flag<BATCH>(err, 4, st);
     }
     return;
   } else {
@@ -241,53 +249,45 @@ __global__ __launch_bounds__(256) void k_nl_search(
     }
   }
 }
+// The entry points own the sort keys (four waves, four centres per workgroup)
+// and name the wave's centre.  Single and rank build: the geometry by value.
+template <bool FILL, bool RANK>
+__global__ __launch_bounds__(256) void k_nl_search(
+    int n, const double* __restrict__ pos, NlGeom G, const int* __restrict__ f0,
+    const int* __restrict__ bin, const int* __restrict__ bin_start,
+    const int* __restrict__ bin_atoms, int* __restrict__ deg, const int* __restrict__ row_ptr,
+    int* __restrict__ center, int* __restrict__ nbr, int* __restrict__ shift,
+    float* __restrict__ vec, int* __restrict__ err, NlRank rk) {
+  __shared__ unsigned long long keys[4][NL_MAXD];
+  const int wid = threadIdx.x >> 6;
+  const int ci = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wid);
+  if (ci >= n) return;
+  nl_search<FILL, RANK, false>(ci, pos, G, 0, 0, keys[wid], f0, bin, bin_start, bin_atoms, deg,
+                               row_ptr, center, nbr, shift, vec, err, rk);
+}
+// Batch: the geometry of the centre's structure, a wave-uniform address.
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_nlb_search(
+    int n, const double* __restrict__ pos, const NlGeomB* __restrict__ geoms,
+    const int* __restrict__ batch, const int* __restrict__ f0, const int* __restrict__ bin,
+    const int* __restrict__ bin_start, const int* __restrict__ bin_atoms, int* __restrict__ deg,
+    const int* __restrict__ row_ptr, int* __restrict__ center, int* __restrict__ nbr,
+    int* __restrict__ shift, float* __restrict__ vec, int* __restrict__ err) {
+  __shared__ unsigned long long keys[4][NL_MAXD];
+  const int wid = threadIdx.x >> 6;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wid);
+  if (i >= n) return;
+  const int st = __builtin_amdgcn_readfirstlane(batch[i]);
+  nl_search<FILL, false, true>(i, pos, geoms[st].G, geoms[st].bin_base, st, keys[wid], f0, bin,
+                               bin_start, bin_atoms, deg, row_ptr, center, nbr, shift, vec, err,
+                               NlRank{});
+}
 
 // ---------------------------------------------------------------- rank graph
 // Row order of one rank of a spatial decomposition (parallel.py RankGraph):
 // owned atoms interior-first then boundary, each by id; ghosts by (owner, id).
 // Every position below comes from a scan or a ballot, never from the order in
 // which threads arrive, so the outputs are bitwise reproducible.
-
-// Exclusive scan over many workgroups (the per-atom arrays of the rank graph:
-// k_nl_scan is one workgroup, 2 ms at 778k entries).  Blocks of 1024 entries,
-// four consecutive ones per thread: FINAL = false writes each block's sum,
-// k_nl_scan turns the sums into block offsets (boff, boff[nblk] = total),
-// FINAL = true rescans its block and writes out[0..n] (out[n] = total).
-constexpr int SCAN_BLK = 1024;
-template <bool FINAL>
-__global__ __launch_bounds__(256) void k_rk_scan(int n, const int* __restrict__ cnt,
-                                                 int* __restrict__ bsum,
-                                                 const int* __restrict__ boff,
-                                                 int* __restrict__ out) {
-  __shared__ int part[256];
-  const int t = threadIdx.x;
-  const int base = blockIdx.x * SCAN_BLK + 4 * t;
-  int v[4], s = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    v[k] = base + k < n ? cnt[base + k] : 0;
-    s += v[k];
-  }
-  part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {  // Hillis-Steele inclusive scan
-    const int u = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += u;
-    __syncthreads();
-  }
-  if constexpr (!FINAL) {
-    if (t == 255) bsum[blockIdx.x] = part[255];
-  } else {
-    int run = boff[blockIdx.x] + (part[t] - s);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (base + k < n) out[base + k] = run;
-      run += v[k];
-    }
-    if (blockIdx.x == gridDim.x - 1 && t == 255) out[n] = boff[gridDim.x];
-  }
-}
 
 // mine[a] = 1 for the rank's atoms; owner values outside [0, world) -> err bit 8
 __global__ void k_rk_mark(int n, const int* __restrict__ owner, int rank, int world,
@@ -384,172 +384,12 @@ __global__ void k_rk_recv(int world, int nblk, const int* __restrict__ off,
 // geometry from geoms[batch[row]]; bins are numbered through the whole batch
 // (NlGeomB::bin_base), so the bin arrays, k_nl_place and both scans serve as
 // they are, and a centre only ever meets atoms of its own structure.  The
-// inclusion test is nl_vec / r2 above, unchanged.
+// bodies are nl_bin and nl_search above; what is left here fills batch[] and
+// the per-structure edge offsets.
 
 __global__ void k_nlb_batch(const int* __restrict__ atom_ptr, int* __restrict__ batch) {
   const int s = blockIdx.x;
   for (int a = atom_ptr[s] + threadIdx.x; a < atom_ptr[s + 1]; a += blockDim.x) batch[a] = s;
-}
-
-__device__ __forceinline__ void nlb_flag(int* __restrict__ err, int bit, int slot, int s) {
-  atomicOr(err, bit);
-  atomicMax(err + slot, s + 1);
-}
-
-__global__ void k_nlb_bin(int n, const double* __restrict__ pos,
-                          const NlGeomB* __restrict__ geoms, const int* __restrict__ batch,
-                          int* __restrict__ f0, int* __restrict__ bin,
-                          int* __restrict__ bin_count, int* __restrict__ err) {
-  const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= n) return;
-  const int st = batch[a];
-  const NlGeom& G = geoms[st].G;
-  const double p0 = pos[3 * a] - G.origin[0], p1 = pos[3 * a + 1] - G.origin[1],
-               p2 = pos[3 * a + 2] - G.origin[2];
-  int b[3], fl3[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double f = ((p0 * G.inv[k]) + (p1 * G.inv[3 + k])) + (p2 * G.inv[6 + k]);
-    const double fl = floor(f);
-    const double fw = f - fl;
-    int bk = (int)(fw * G.nb[k]);
-    bk = bk < 0 ? 0 : (bk >= G.nb[k] ? G.nb[k] - 1 : bk);
-    b[k] = bk;
-    if (!(fl > -1e9 && fl < 1e9)) nlb_flag(err, 1, 1, st);  // non-finite or absurd position
-    fl3[k] = (int)fl;
-    f0[3 * a + k] = fl3[k];
-  }
-  if (!G.periodic && (fl3[0] | fl3[1] | fl3[2])) nlb_flag(err, 1, 1, st);
-  const int id = geoms[st].bin_base + ((b[0] * G.nb[1] + b[1]) * G.nb[2] + b[2]);
-  bin[a] = id;
-  atomicAdd(&bin_count[id], 1);
-}
-
-// k_nl_search<FILL, false> with the geometry per structure; rows, bins and keys
-// are those of the concatenated batch, so a structure's edges come out in the
-// single build's order with its first row added to i and j
-template <bool FILL>
-__global__ __launch_bounds__(256) void k_nlb_search(
-    int n, const double* __restrict__ pos, const NlGeomB* __restrict__ geoms,
-    const int* __restrict__ batch, const int* __restrict__ f0, const int* __restrict__ bin,
-    const int* __restrict__ bin_start, const int* __restrict__ bin_atoms, int* __restrict__ deg,
-    const int* __restrict__ row_ptr, int* __restrict__ center, int* __restrict__ nbr,
-    int* __restrict__ shift, float* __restrict__ vec, int* __restrict__ err) {
-  __shared__ unsigned long long keys[4][NL_MAXD];
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wid);
-  if (i >= n) return;
-  const int st = __builtin_amdgcn_readfirstlane(batch[i]);
-  const NlGeom& G = geoms[st].G;  // wave-uniform address
-  const int bin_base = geoms[st].bin_base;
-  const int nb[3] = {G.nb[0], G.nb[1], G.nb[2]};
-  const int R[3] = {G.R[0], G.R[1], G.R[2]};
-  const int periodic = G.periodic;
-  unsigned long long* K = keys[wid];
-  const int bi = bin[i] - bin_base;
-  const int b[3] = {bi / (nb[1] * nb[2]), (bi / nb[2]) % nb[1], bi % nb[2]};
-  const int fi[3] = {f0[3 * i], f0[3 * i + 1], f0[3 * i + 2]};
-  const double rc2 = G.rc2;
-  int count = 0;  // uniform
-  for (int ox = -R[0]; ox <= R[0]; ++ox)
-    for (int oy = -R[1]; oy <= R[1]; ++oy)
-      for (int oz = -R[2]; oz <= R[2]; ++oz) {
-        const int o[3] = {ox, oy, oz};
-        int c[3], sh[3];
-        bool skip = false;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const int v = b[k] + o[k];
-          if (periodic) {
-            sh[k] = v >= 0 ? v / nb[k] : -((-v + nb[k] - 1) / nb[k]);
-            c[k] = v - sh[k] * nb[k];
-          } else {
-            sh[k] = 0;
-            c[k] = v;
-            skip |= v < 0 || v >= nb[k];
-          }
-        }
-        if (skip) continue;
-        const int id = bin_base + ((c[0] * nb[1] + c[1]) * nb[2] + c[2]);
-        const int s = bin_start[id], e = bin_start[id + 1];
-        for (int t0 = s; t0 < e; t0 += 64) {
-          const int t = t0 + lane;
-          bool hit = false;
-          int j = 0, S[3] = {0, 0, 0};
-          if (t < e) {
-            j = bin_atoms[t];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) S[k] = sh[k] + fi[k] - f0[3 * j + k];
-            const Hit h = nl_vec(pos, G, i, j, S[0], S[1], S[2]);
-            const double r2 = ((h.d[0] * h.d[0]) + (h.d[1] * h.d[1])) + (h.d[2] * h.d[2]);
-            hit = r2 < rc2 && !(j == i && S[0] == 0 && S[1] == 0 && S[2] == 0);
-          }
-          const unsigned long long m = __ballot(hit);
-          if (FILL && hit) {
-            const int slot = count + __popcll(m & ((1ull << lane) - 1));
-            const int lim = 1 << SB;
-            if (S[0] < -lim || S[0] >= lim || S[1] < -lim || S[1] >= lim || S[2] < -lim ||
-                S[2] >= lim)
-              nlb_flag(err, 2, 2, st);
-            else if (slot < NL_MAXD)
-              K[slot] = nl_key(j, S[0], S[1], S[2]);
-          }
-          count += __popcll(m);
-        }
-      }
-  if constexpr (!FILL) {
-    if (lane == 0) {
-      deg[i] = count;
-      if (count > NL_MAXD) nlb_flag(err, 4, 3, st);
-    }
-    return;
-  } else {
-    if (count > NL_MAXD) return;  // reported by the count pass
-    // bitonic sort of K[0..P) (P = next power of two; padding = max key)
-    int P = 1;
-    while (P < count) P <<= 1;
-    for (int t = count + lane; t < P; t += 64) K[t] = ~0ull;
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    for (int k = 2; k <= P; k <<= 1)
-      for (int jj = k >> 1; jj > 0; jj >>= 1) {
-        for (int t = lane; t < P; t += 64) {
-          const int u = t ^ jj;
-          if (u > t) {
-            const unsigned long long a = K[t], c = K[u];
-            const bool up = (t & k) == 0;
-            if ((a > c) == up) {
-              K[t] = c;
-              K[u] = a;
-            }
-          }
-        }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      }
-    const int base = row_ptr[i];
-    for (int t = lane; t < count; t += 64) {
-      const unsigned long long key = K[t];
-      const int j = (int)(key >> 33);
-      const int sx = (int)((key >> 22) & 0x7ff) - (1 << SB);
-      const int sy = (int)((key >> 11) & 0x7ff) - (1 << SB);
-      const int sz = (int)(key & 0x7ff) - (1 << SB);
-      const Hit h = nl_vec(pos, G, i, j, sx, sy, sz);
-      const int64_t q = (int64_t)base + t;
-      center[q] = i;
-      nbr[q] = j;
-      if (shift) {
-        shift[3 * q] = sx;
-        shift[3 * q + 1] = sy;
-        shift[3 * q + 2] = sz;
-      }
-      if (vec) {
-        vec[3 * q] = (float)h.d[0];
-        vec[3 * q + 1] = (float)h.d[1];
-        vec[3 * q + 2] = (float)h.d[2];
-      }
-    }
-  }
 }
 
 __global__ void k_nlb_edge_ptr(int B, const int* __restrict__ atom_ptr,
@@ -572,10 +412,6 @@ hipError_t launch_nl_place(int n, const int* bin, const int* bin_start, int* cur
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_nl_place, dim3((n + 255) / 256), dim3(256), 0, s, n, bin, bin_start,
                      cursor, bin_atoms);
-  return hipGetLastError();
-}
-hipError_t launch_nl_scan(int n, const int* cnt, int* out, hipStream_t s) {
-  hipLaunchKernelGGL(k_nl_scan, dim3(1), dim3(1024), 0, s, n, cnt, out);
   return hipGetLastError();
 }
 hipError_t launch_nl_search(bool fill, int n, const double* pos, const NlGeom& G, const int* f0,
@@ -605,15 +441,6 @@ hipError_t launch_nl_rank_search(bool fill, int nc, const double* pos, const NlG
   else
     hipLaunchKernelGGL((k_nl_search<false, true>), grid, block, 0, s, nc, pos, G, f0, bin,
                        bin_start, bin_atoms, deg, row_ptr, center, nbr, shift, vec, err, rk);
-  return hipGetLastError();
-}
-int nl_scan_blocks(int n) { return n > 0 ? (n + SCAN_BLK - 1) / SCAN_BLK : 1; }
-hipError_t launch_rk_scan(int n, const int* cnt, int* out, int* bsum, int* boff, hipStream_t s) {
-  const int nblk = nl_scan_blocks(n);
-  hipLaunchKernelGGL(k_rk_scan<false>, dim3(nblk), dim3(256), 0, s, n, cnt, bsum, nullptr,
-                     nullptr);
-  hipLaunchKernelGGL(k_nl_scan, dim3(1), dim3(1024), 0, s, nblk, bsum, boff);
-  hipLaunchKernelGGL(k_rk_scan<true>, dim3(nblk), dim3(256), 0, s, n, cnt, nullptr, boff, out);
   return hipGetLastError();
 }
 hipError_t launch_rk_mark(int n, const int* owner, int rank, int world, int* mine, int* err,

@@ -127,7 +127,7 @@ def test_batch_graph_is_reproducible(dnl, S):
 
 def test_batch_graph_awkward_cells(dnl):
     """The cells of tests/_cells.py in one batch: per-structure geometry, bins
-    and stencils of k_nlb_search on a sheared cell, an unreduced lattice (R > 1
+    and stencils of the batched search on a sheared cell, an unreduced lattice (R > 1
     on one axis), a halved bin grid, and degrees 64 and 512 (the cap) beside
     them.  The host lists they are compared with equal the brute force
     (tests/test_cells_host.py)."""

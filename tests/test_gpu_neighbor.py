@@ -213,3 +213,56 @@ def test_degree_513_is_refused(dnl):
         dnl(pos, None, 5.0, (False, False, False))
     pos, cell, _ = C.sparse_box()
     check(dnl, pos, cell)
+
+
+# ------------------------------------------- refusals the device reports, three forms
+CELL6 = np.eye(3) * 6.0
+PAIR = np.array([[0.0, 0.0, 0.0], [3.0, 0.0, 0.0]])
+FORMS = ('single', 'rank', 'batch')
+
+
+def build_form(dnl, form, pos):
+    """(ei, sh) of (pos, CELL6) at cutoff 5 from the single build, the rank build
+    (world 1: local rows are the atom ids) or the batch build, where the structure
+    stands second, behind the healthy PAIR."""
+    if form == 'single':
+        c, n, s, _ = dnl(pos, CELL6, 5.0)
+    elif form == 'rank':
+        d = dnl.rank_graph(pos, CELL6, 5.0, np.zeros(len(pos), dtype=np.int32), 0, 1)
+        c, n, s = d['center'], d['nbr'], d['shift']
+    else:
+        c, n, s, _, ap, ep = dnl.batch([PAIR, pos], [CELL6, CELL6], 5.0)
+        b, e = int(ep[1]), int(ep[2])
+        c, n, s = c[b:e] - int(ap[1]), n[b:e] - int(ap[1]), s[b:e]
+    return (np.stack([c.cpu().numpy(), n.cpu().numpy()]).astype(np.int64),
+            s.cpu().numpy().astype(np.float64))
+
+
+def refused(dnl, form, pos, what):
+    """The build (or its fetch) raises `what`, the batch naming structure 1;
+    afterwards the same handle builds the healthy cell as the host list has it."""
+    from sevennet_finetuning_amd._lib import E3GNNError
+    with pytest.raises(E3GNNError, match='structure 1.*' + what if form == 'batch' else what):
+        build_form(dnl, form, pos)
+    ei, sh = build_form(dnl, form, PAIR)
+    ej, sj = neighbor_list(PAIR, CELL6, 5.0)
+    assert ej.shape[1] == 4
+    assert np.array_equal(ei, ej) and np.array_equal(sh, sj)
+
+
+@pytest.mark.parametrize('form', FORMS)
+def test_shift_beyond_1024_cells_is_refused(dnl, form):
+    """The second atom 2000 cells along a: every edge has |Sx| of 2000 or 2001,
+    more than the sort key holds.  The fill pass flags it and still sorts and
+    writes keys it can index with."""
+    far = PAIR + np.array([[0.0, 0.0, 0.0], [2000 * 6.0, 0.0, 0.0]])
+    ei, sh = neighbor_list(far, CELL6, 5.0)
+    assert ei.shape[1] == 4 and set(np.abs(sh[:, 0]).tolist()) == {2000, 2001}
+    refused(dnl, form, far, '1024')
+
+
+@pytest.mark.parametrize('form', FORMS)
+def test_non_finite_position_is_refused(dnl, form):
+    bad = PAIR.copy()
+    bad[1, 1] = np.nan
+    refused(dnl, form, bad, 'non-finite')

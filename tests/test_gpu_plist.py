@@ -102,6 +102,46 @@ def test_rows_at_the_wave_boundaries(flt):
     _assert_same(_run(flt, L), ref)
 
 
+# ------------------------------------------------------------ scan boundaries
+SCAN_BLOCK = 1024        # rows per workgroup of the scan of the degrees (csrc/scan.hip)
+SCAN_N = (1, 1023, 1024, 1025, 4096, 4097, 1024 * 1024 + 1025)   # 4096: the last one-workgroup n
+
+
+def _scan_case(n):
+    """n rows over n + 1 atoms, the maps the identity.  Atom a < n sits at
+    (0.1 (a mod 7), 0, 0), atom n at (100, 0, 0) with graph row 0.  Row t has 0-3
+    candidates, each either (t + 1) mod n (a hit) or atom n (a miss)."""
+    rng = np.random.default_rng(n)
+    x = np.zeros((n + 1, 3))
+    x[:n, 0] = 0.1 * (np.arange(n) % 7)
+    x[n, 0] = 100.0
+    ncand = rng.integers(0, 4, size=n)
+    rows = np.repeat(np.arange(n), ncand)
+    cand = np.where(rng.integers(0, 2, size=len(rows)) == 1, (rows + 1) % n, n)
+    atom_row = np.arange(n + 1, dtype=np.int32)
+    atom_row[n] = 0
+    return dict(x=x, row_atom=np.arange(n, dtype=np.int32), atom_row=atom_row,
+                cand_ptr=np.concatenate([[0], np.cumsum(ncand)]).astype(np.int64),
+                cand=cand.astype(np.int32))
+
+
+@pytest.mark.parametrize('n', SCAN_N)
+def test_row_offsets_at_the_scan_boundaries(flt, n):
+    """Rows of any degree from 0 to 3, so ``center`` is exactly repeat(arange(n),
+    deg): one row, one short of a scan block, a block, one more (the carry of
+    the one-workgroup scan), the last n it serves and the first of the scan over
+    many workgroups, and more than 1,024 blocks (the carry over the block totals)."""
+    L = _scan_case(n)
+    ref = filter_ref(L['x'], L['row_atom'], L['cand_ptr'], L['cand'], NEIGHMASK, L['atom_row'], RC)
+    deg = np.bincount(ref[0], minlength=n)
+    assert np.array_equal(ref[0], np.repeat(np.arange(n), deg))
+    if n > 1:                                            # one row has one degree
+        assert deg.min() == 0 and deg.max() == 3
+    if n == SCAN_N[-1]:
+        assert -(-n // SCAN_BLOCK) > 1024
+    _assert_same(_run(flt, L), ref)
+
+
 def test_the_cutoff_is_strict(flt):
     """d^2 = rc^2 exactly is no edge; one ulp inside is."""
     inside = np.nextafter(5.0, 0.0)
