@@ -116,6 +116,10 @@ struct e3gnn_ctx {
   // graph
   DBuf type, center, nbr, vec, row_ptr, src_ptr, src_perm, cnt, err;
   DBuf Y, emb, dY, dgu, demb, fe;
+  // the fused kernels take the radial MLP's share of dE/dr in forward mode:
+  // embd = d emb / dr [E, 8] in, drad [E] accumulated over the blocks (demb,
+  // dE/demb, is the v1 kernels')
+  DBuf embd, drad;
   // node linears on k_nodelin (node-aligned tiles, si2 + sc in one problem,
   // gate in the epilogue; 1, default) or the grouped k_gemm + k_gate kernels
   // (0; E3GNN_NODELIN=0)
@@ -335,15 +339,13 @@ void dense_cg(float* out) {
 }
 MlpW mlp_ptrs(const e3gnn_model* m, int t) {
   const auto& mm = m->mlp[t];
-  return MlpW{mm.w0.f(),
-              mm.w2r.f(),
-              static_cast<const uint16_t*>(mm.w2b.p),
-              static_cast<const uint16_t*>(mm.w2d.p),
-              static_cast<const uint16_t*>(mm.w2v.p),
-              static_cast<const uint16_t*>(mm.w2s.p),
-              static_cast<const uint16_t*>(mm.w1b.p),
-              static_cast<const uint16_t*>(mm.w1tb.p),
-              static_cast<const uint16_t*>(mm.w0tb.p)};
+  MlpW w{};   // (the retired slots stay null)
+  w.w0 = mm.w0.f();
+  w.w2b = static_cast<const uint16_t*>(mm.w2b.p);
+  w.w2v = static_cast<const uint16_t*>(mm.w2v.p);
+  w.w2s = static_cast<const uint16_t*>(mm.w2s.p);
+  w.w1b = static_cast<const uint16_t*>(mm.w1b.p);
+  return w;
 }
 
 // What every fused launch of block t shares (fused.h): the graph, the edge
@@ -457,14 +459,17 @@ int e3gnn_graph_set(e3gnn_ctx* c, int64_t n_local, int64_t n_ghost, int64_t n_ed
     HIPCHK(c->Y.ensure(E * 9 * F));
     HIPCHK(c->emb.ensure(E * 8 * F));
     HIPCHK(c->dY.ensure(E * 9 * F));
-    HIPCHK(c->demb.ensure(E * 8 * F));
     HIPCHK(c->fe.ensure(E * 3 * F));
     HIPCHK(c->dgu.ensure(E * 3 * F));
     const bool v1 = c->impl == 1;
     c->graph_impl = c->impl;
     if (v1) {
+      HIPCHK(c->demb.ensure(E * 8 * F));
       HIPCHK(c->H1.ensure(E * 64 * F));
       HIPCHK(c->H2.ensure(E * 64 * F));
+    } else {
+      HIPCHK(c->embd.ensure(E * 8 * F));
+      HIPCHK(c->drad.ensure(E * F));
     }
     int maxW = 0, maxDM = 0;
     for (int t = 0; t < m->nlayer; ++t) {
@@ -532,16 +537,17 @@ int e3gnn_graph_set(e3gnn_ctx* c, int64_t n_local, int64_t n_ghost, int64_t n_ed
   }
   if (c->gen) return E3GNN_OK;  // (edge embedding done by gen_graph_set)
   {
-    Region r(c, s, C_EMBED_EDGE, 0, (double)E * (12 + 68));
+    Region r(c, s, C_EMBED_EDGE, 0, (double)E * (12 + 68 + (c->graph_impl == 1 ? 0 : 32)));
     HIPCHK(launch_edge_embed(E, c->vec.f(), m->coeffs.f(), m->cutoff, m->r_on, m->raw_sh, c->Y.f(),
-                             c->emb.f(), s));
+                             c->emb.f(), c->graph_impl == 1 ? nullptr : c->embd.f(), s));
   }
   if (E > 0) {
     // zero kernels, not hipMemsetAsync: the evaluation stays correct when a
     // host captures it in a HIP graph (launch_zero, node.hip)
     HIPCHK(launch_zero(c->dY.f(), E * 9, s));
     HIPCHK(launch_zero(c->dgu.f(), E * 3, s));
-    HIPCHK(launch_zero(c->demb.f(), E * 8, s));
+    if (c->graph_impl == 1) HIPCHK(launch_zero(c->demb.f(), E * 8, s));
+    else HIPCHK(launch_zero(c->drad.f(), E, s));
   }
   return E3GNN_OK;
 }
@@ -906,7 +912,8 @@ int e3gnn_layer_backward_part(e3gnn_ctx* c, int t, int part, void* stream) {
   a.dh = c->dh.f();  // the last block writes its dE/dx rows here
   a.dxc = (!last && t > 0) ? c->dxc.f() : nullptr;
   a.dgu = c->dgu.f();
-  a.demb = c->demb.f();
+  a.embd = c->embd.f();
+  a.drad = c->drad.f();
   // part 0: boundary centres / their edges / ghost neighbour nodes
   a.c_begin = (int)(part == 0 ? n_int : 0);
   a.c_end = (int)(part == 0 ? nl : n_int);
@@ -955,9 +962,10 @@ int e3gnn_forces(e3gnn_ctx* c, float* forces, float* virial6, float* edge_grad, 
   }
   const int64_t n = c->n, nl = c->nl, E = c->E;
   {
-    Region r(c, s, C_EDGE_FORCE, 0, (double)E * 4 * (3 + 9 + 8 + 3));
+    Region r(c, s, C_EDGE_FORCE, 0, (double)E * 4 * (3 + 9 + (c->graph_impl == 1 ? 8 : 1) + 3));
     HIPCHK(launch_edge_force(E, c->vec.f(), m->coeffs.f(), m->cutoff, m->r_on, m->raw_sh, c->dY.f(),
-                             c->dgu.f(), c->demb.f(), c->fe.f(), c->vpart.f(), s));
+                             c->dgu.f(), c->graph_impl == 1 ? c->demb.f() : nullptr,
+                             c->graph_impl == 1 ? nullptr : c->drad.f(), c->fe.f(), c->vpart.f(), s));
     HIPCHK(launch_final_sum(edge_force_blocks(E), 6, c->vpart.f(),
                             virial6 ? virial6 : c->scratch6.f(), s));
   }
@@ -1171,7 +1179,9 @@ float* e3gnn_debug_ptr(e3gnn_ctx* c, const char* name, int layer, int64_t* numel
   else if (n == "emb") { p = c->emb.f(); k = c->E * 8; }
   else if (n == "dY") { p = c->dY.f(); k = c->E * 9; }
   else if (n == "dgu") { p = c->dgu.f(); k = c->E * 3; }
-  else if (n == "demb") { p = c->demb.f(); k = c->E * 8; }
+  else if (n == "demb" && c->graph_impl == 1) { p = c->demb.f(); k = c->E * 8; }
+  else if (n == "embd" && c->graph_impl != 1) { p = c->embd.f(); k = c->E * 8; }
+  else if (n == "drad" && c->graph_impl != 1) { p = c->drad.f(); k = c->E; }
   else if (n == "dxc") { p = c->dxc.f(); k = c->E * 480; }
   else if (n == "fe") { p = c->fe.f(); k = c->E * 3; }
   if (numel) *numel = p ? k : 0;
@@ -1183,6 +1193,7 @@ int64_t e3gnn_workspace_bytes(const e3gnn_ctx* c) {
   int64_t b = 0;
   const DBuf* fixed[] = {&c->type, &c->center, &c->nbr, &c->vec, &c->row_ptr, &c->src_ptr,
                          &c->src_perm, &c->cnt, &c->err, &c->Y, &c->emb, &c->dY, &c->dgu, &c->demb,
+                         &c->embd, &c->drad,
                          &c->fe, &c->H1, &c->H2, &c->agg, &c->dw, &c->dxc, &c->dy, &c->dh,
                          &c->eat, &c->part, &c->vpart, &c->scratch6, &c->beat, &c->bw};
   for (auto* d : fixed) b += (int64_t)d->cap;

@@ -409,7 +409,7 @@ int e3gnn_edge_geometry(int64_t n_edges, const float* vec, const float* coeffs, 
                         int raw_sh, float* Y, float* emb, void* stream) {
   if (n_edges <= 0) return E3GNN_OK;
   if (!vec || !coeffs || !Y || !emb) return fail(E3GNN_ERR_ARG, "null edge geometry operand");
-  HIPCHK(launch_edge_embed(n_edges, vec, coeffs, rc, ron, raw_sh, Y, emb, (hipStream_t)stream));
+  HIPCHK(launch_edge_embed(n_edges, vec, coeffs, rc, ron, raw_sh, Y, emb, nullptr, (hipStream_t)stream));
   return E3GNN_OK;
 }
 
@@ -431,7 +431,7 @@ int e3gnn_edge_geometry_vjp(int64_t n_edges, const float* vec, const float* coef
                             void* stream) {
   if (n_edges <= 0) return E3GNN_OK;
   if (!vec || !coeffs || !Yb || !embb || !fij) return fail(E3GNN_ERR_ARG, "null edge geometry operand");
-  HIPCHK(launch_edge_force(n_edges, vec, coeffs, rc, ron, raw_sh, Yb, nullptr, embb, fij, nullptr,
+  HIPCHK(launch_edge_force(n_edges, vec, coeffs, rc, ron, raw_sh, Yb, nullptr, embb, nullptr, fij, nullptr,
                            (hipStream_t)stream));
   return E3GNN_OK;
 }

@@ -5,34 +5,34 @@
 
 namespace e3gnn {
 
+// The struct is a kernel argument of the forward kernels too: the slots of the
+// operands that only the reverse-mode radial backward read (W2 in the dH2
+// orders, W1^T, W0^T) are kept, null, so that the forward kernels' argument
+// layout -- and with it their code objects and the bits of the energy -- stay
+// what they were (DESIGN.md 8 records how a change there once moved atomic
+// energies by an ulp).
 struct MlpW {
   const float* w0;   // [8][64]   layer0 / sqrt(8)
-  // w2 = layer2 / 8 ([64][W]) in the f32 operand order of the last block's
-  // backward in its six-product reference form (E3GNN_DH2_X3=0):
-  const float* w2r;  // [n/16][bh][g][c][r] = w2[16bh + c][16(n/16) + 4g + r]
-  // w2 as three bf16 pieces (w2 = p0 + p1 + p2, exact) in v_mfma_f32_16x16x32_bf16
-  // operand order: [n/16][piece][m][g][c][t] = piece of w2[16(2m + t/4) + 4g + t%4][n]
+  const float* retired0;
+  // w2 = layer2 / 8 ([64][W]) as three bf16 pieces (w2 = p0 + p1 + p2, exact) in
+  // v_mfma_f32_16x16x32_bf16 operand order: [n/16][piece][m][g][c][t] = piece of
+  // w2[16(2m + t/4) + 4g + t%4][n]
   const uint16_t* w2b;
-  // the last block's dH2 operand over PAIRS of consecutive visited 16-column
-  // blocks (model_load.cpp bwd_w_block_cols): [pair][piece][bh][g][c][t] = piece of
-  // w2[16 bh + c][col], col = channel 4g + t of the pair's first block (t < 4)
-  // or 4g + t - 4 of its second (last block only; null elsewhere)
-  const uint16_t* w2d;
-  // w2b's column blocks in the kernels' visiting order (block k at column 16 k):
-  // the software-pipelined loops fetch the operand of the block after next
-  // (last block only; null elsewhere)
+  const uint16_t* retired1;
+  // w2b's column blocks in the kernels' visiting order (block k at column 16 k;
+  // model_load.cpp bwd_w_block_cols): the software-pipelined loops fetch the
+  // operand of the block after next (last block only; null elsewhere)
   const uint16_t* w2v;
-  // the lock-step backward's one image per PAIR (w2_image.h): [pair][piece]
-  // [hidden unit][swizzled 8-byte unit of 4 channels of one of the pair's two
-  // blocks], staged in LDS by a straight copy; its row reads are w2d's lane
-  // registers, its transposed reads w2v's (first / middle blocks only)
+  // the lock-step backward's one image per PAIR of visited blocks (w2_image.h):
+  // [pair][piece][hidden unit][swizzled 8-byte unit of 4 channels of one of the
+  // pair's two blocks], staged in LDS by a straight copy; its transposed reads
+  // are w2v's lane registers (first / middle blocks only)
   const uint16_t* w2s;
-  // the radial MLP's other bf16x6 products, in w2b's operand order: W1 (layer
-  // 1 forward, 64 columns), W1^T (dH1 = dA2 W1^T) and W0^T padded to 16 columns
-  // (demb = dA1 W0^T)
+  // layer 1 (W1, 64 columns) in w2b's operand order: the value's and the
+  // backward tangent's operand
   const uint16_t* w1b;
-  const uint16_t* w1tb;
-  const uint16_t* w0tb;
+  const uint16_t* retired2;
+  const uint16_t* retired3;
 };
 
 struct FusedArgs {
@@ -49,7 +49,10 @@ struct FusedArgs {
   float* dh;           // bwd out [n_nodes, DX]: dE/dx of the gathered features (last block)
   float* dxc;          // [E, DX] per-edge dE/dx (first / middle blocks; null: not stored)
   float* dgu;         // bwd in/out [E, 3]  dE/du accumulated over layers
-  float* demb;        // bwd in/out [E, 8]  dE/demb accumulated over layers
+  // the radial MLP's share of dE/dr in forward mode: sum over the block's
+  // weights of dE/dw . dw/dr, the tangent dw/dr run through the MLP from embd
+  const float* embd;  // bwd in     [E, 8]  d emb / dr (node.hip k_edge_embed)
+  float* drad;        // bwd in/out [E]     dE/dr |radial accumulated over layers
   MlpW W;
   int n_centers;
   int n_edges;
@@ -68,11 +71,11 @@ struct FusedArgs {
 hipError_t launch_conv_fwd(int kind, const FusedArgs& a, hipStream_t s);
 // backward of a first / middle block: the lock-step kernel (rounds of four
 // consecutive 16-edge tiles of the range [e_begin, e_end) per workgroup, W2
-// operands staged per block pair in LDS, dH2 on bf16x6), per-edge
-// dE/dx to dxc, dE/du, dE/dw -> dE/demb
+// operands staged per block pair in LDS), per-edge dE/dx to dxc, dE/du,
+// dE/dw . dw/dr -> drad
 hipError_t launch_conv_bwd_ls(int kind, const FusedArgs& a, hipStream_t s);
 // backward of the last block, one wave per neighbour node: dE/dx to dh, dE/du,
-// dE/dw -> dE/demb
+// dE/dw . dw/dr -> drad
 hipError_t launch_conv_bwd_nbr_last(int kind, const FusedArgs& a, hipStream_t s);
 
 }  // namespace e3gnn

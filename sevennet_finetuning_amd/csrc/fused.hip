@@ -23,8 +23,9 @@
 //     centre's row in LDS.  Backward (lock-step, four consecutive 16-edge
 //     tiles per round whatever their centres, W2 pieces staged per block
 //     pair in LDS): w^T recomputed, lane (g, c) =
-//     edge c x channels 4g..4g+3; dE/dx per edge, dE/dY -> dE/du, dE/dw ->
-//     dH2 (bf16x6 over the pair) -> MLP chain -> dE/demb.
+//     edge c x channels 4g..4g+3; dE/dx per edge, dE/dY -> dE/du, and the
+//     radial MLP's share of dE/dr in forward mode: dE/dw . w', the tangent
+//     w' = dw/dr formed beside w from the same W2 operand registers.
 //   * Weights via buffer descriptors (scalar k offsets, one VGPR of lane offset).
 // Deterministic: no atomics; every sum has a fixed order.
 #include "cg_tables.h"
@@ -124,16 +125,14 @@ __device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
 // does not hoist hundreds of 64-bit addresses out of the centre loop (which it
 // did, and spilled).  Offsets outside the descriptor read 0 (padded rows).
 struct WRes {
-  __amdgpu_buffer_rsrc_t w0, w2b, w2r, w2d, w2v, w1b, w1tb, w0tb;
+  __amdgpu_buffer_rsrc_t w0, w2b, w2v, w1b;
 };
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const float* p, int nfloats) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, nfloats * 4, 0x00020000);
 }
 __device__ __forceinline__ WRes make_wres(const MlpW& W, int width) {
-  return {rsrc(W.w0, 8 * 64), rsrc((const float*)W.w2b, 64 * width * 3 / 2), rsrc(W.w2r, 64 * width),
-          rsrc((const float*)W.w2d, 64 * width * 3 / 2),
-          rsrc((const float*)W.w2v, 64 * width * 3 / 2), rsrc((const float*)W.w1b, 64 * 64 * 3 / 2),
-          rsrc((const float*)W.w1tb, 64 * 64 * 3 / 2), rsrc((const float*)W.w0tb, 64 * 16 * 3 / 2)};
+  return {rsrc(W.w0, 8 * 64), rsrc((const float*)W.w2b, 64 * width * 3 / 2),
+          rsrc((const float*)W.w2v, 64 * width * 3 / 2), rsrc((const float*)W.w1b, 64 * 64 * 3 / 2)};
 }
 __device__ __forceinline__ float ldw(__amdgpu_buffer_rsrc_t r, int vbytes, int sbytes) {
   // the builtin returns the raw 32 bits (an unsigned int): reinterpret, never convert
@@ -240,25 +239,6 @@ __device__ __forceinline__ void split3x8(const float (&v)[8], bf16x8 (&d)[3]) {
   for (int pc = 0; pc < 3; ++pc) d[pc] = __builtin_bit_cast(bf16x8, w[pc]);
 }
 
-// the same in two pieces (v = p0 + p1 + O(2^-16 |v|)): the operand of the
-// three-product (bf16x3) dH2 form below
-__device__ __forceinline__ void split2x8(const float (&v)[8], bf16x8 (&d)[2]) {
-  u32x4 w[2];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    f32x2 r;
-    r[0] = v[2 * q];
-    r[1] = v[2 * q + 1];
-    const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-    w[0][q] = u;
-    r[0] -= __builtin_bit_cast(float, u << 16);
-    r[1] -= __builtin_bit_cast(float, u & 0xffff0000u);
-    w[1][q] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-  }
-  d[0] = __builtin_bit_cast(bf16x8, w[0]);
-  d[1] = __builtin_bit_cast(bf16x8, w[1]);
-}
-
 // the lane's 16 H2 values (units 16 bh + 4g + r) as three bf16 pieces
 __device__ __forceinline__ void split_h2(const f32x4 (&h2)[4], Op3& o) {
 #pragma unroll
@@ -310,6 +290,21 @@ __device__ __forceinline__ f32x4 w2_block_bwd(const Op3& h, const Op3& w) {
   if constexpr (E3GNN_BWD_W_X3) return w2_block3<HA>(h, w);
   else return w2_block<HA>(h, w);
 }
+// the backward kernels' tangent product w' = W2^T H2'^T (mlp_chain_jvp): the
+// w recompute's W2 operand registers against the pieces of H2'.  It took the
+// place of the reverse-mode dH2 = dw W2^T and keeps that product's switch:
+// three bf16 products by default (dropped terms ~2^-16 of w'; the dH2 form's
+// measurements on the reference KAT systems: force errors 2.9e-6 .. 2.1e-5
+// against the six-product build's 3.1e-6 .. 1.9e-5 eV/A, tolerance 1e-4),
+// E3GNN_DH2_X3=0: six
+#ifndef E3GNN_DH2_X3
+#define E3GNN_DH2_X3 1
+#endif
+template <bool HA>
+__device__ __forceinline__ f32x4 w2_block_tan(const Op3& hd, const Op3& w) {
+  if constexpr (E3GNN_DH2_X3) return w2_block3<HA>(hd, w);
+  else return w2_block<HA>(hd, w);
+}
 
 // ---------------------------------------------------------------- radial MLP
 // Tile of 16 edge slots [e0, e0+16) (slots >= e1 are zero rows).
@@ -334,20 +329,17 @@ __device__ __forceinline__ void mlp_layer0(const WRes& R, const float (&b)[2], i
     a1[bh] = acc;
   }
 }
-// The backward kernels' MLP-chain products (the layer-1 recompute and the
-// chain backward's dH1 / dE/demb) on three bf16 products like dH2 and the w
-// recompute (E3GNN_CHAIN_X3, default; =0 six); the forward, whose chain gives
-// the energy, keeps six.  Same box: step 39.8 -> 39.2 ms (first / middle /
-// last backward 1.68 / 5.28 / 2.06 -> 1.56 / 5.20 / 1.92 ms); parity, full-size
-// and family tests green; NVE drift over 2,000 steps 1.67e-4 meV/atom/ps
-// against 1.38e-4 (six-product chains) and 1.19e-4 (exact-gradient generic
-// engine), excursions identical (profiles/r06_s18_*)
+// The backward kernels' layer-1 products (the recompute and its tangent, see
+// mlp_chain_jvp) on three bf16 products like the w recompute (E3GNN_CHAIN_X3,
+// default; =0 six); the forward, whose chain gives the energy, keeps six.
+// Measured with the reverse-mode chain this replaced: step 39.8 -> 39.2 ms;
+// parity, full-size and family tests green; NVE drift over 2,000 steps 1.67e-4
+// meV/atom/ps against 1.38e-4 (six-product chains) and 1.19e-4 (exact-gradient
+// generic engine), excursions identical (profiles/r06_s18_*)
 #ifndef E3GNN_CHAIN_X3
 #define E3GNN_CHAIN_X3 1
 #endif
 constexpr bool CX3 = E3GNN_CHAIN_X3 != 0;
-// X3: layer 1 on three bf16 products
-template <bool X3 = false>
 __device__ __forceinline__ void mlp_chain(const WRes& R, const float (&b)[2], int lane, MlpT& m) {
   mlp_layer0(R, b, lane, m.a1);
   Op3 hq;
@@ -364,8 +356,61 @@ __device__ __forceinline__ void mlp_chain(const WRes& R, const float (&b)[2], in
     phase();
     Op3 wq;
     load_w2b(wq, R.w1b, lane, 16 * bo);
-    m.a2[bo] = X3 ? w2_block3<false>(hq, wq) : w2_block<false>(hq, wq);
+    m.a2[bo] = w2_block<false>(hq, wq);
   }
+}
+
+// The backward kernels' chain: the tile's H2 and its TANGENT H2' = dH2/dr, in
+// the w product's operand pieces.  The radial MLP has one scalar input, r, so
+// the radial share of dE/dr is taken in forward mode: emb' = d emb / dr
+// (k_edge_embed's embd; b / bd = the lane's emb / emb' values, mlp_pre's
+// order; padded slots 0) runs through the same layers,
+//   a1' = W0^T emb',  H1' = act'(a1) a1',  a2' = W1^T H1',  H2' = act'(a2) a2',
+// every W0 fragment and W1 operand block loaded once for value and tangent
+// (the products of E3GNN_CHAIN_X3 for both), and the kernels contract
+// w' = W2^T H2' with the dE/dw they hold in w's layout.  No W1^T / W0^T
+// operands, no dH2 accumulators and no pre-activations kept to the tile end.
+__device__ __forceinline__ void mlp_chain_jvp(const WRes& R, const float (&b)[2], const float (&bd)[2], int lane,
+                                              Op3& h2q, Op3& h2dq) {
+  const int g = lane >> 4, c = lane & 15;
+  const int v0 = (g * 64 + c) * 4;  // W0s[4s + g][16 bh + c]
+  Op3 hq, hdq;
+  {
+    f32x4 h1[4], h1d[4];
+#pragma unroll
+    for (int bh = 0; bh < 4; ++bh) {
+      f32x4 acc = zero4(), accd = zero4();
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const float w = ldw(R.w0, v0, (4 * s * 64 + 16 * bh) * 4);
+        acc = mfma(w, b[s], acc);
+        accd = mfma(w, bd[s], accd);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        h1[bh][r] = act_fwd(acc[r]);
+        h1d[bh][r] = act_grad(acc[r]) * accd[r];
+      }
+    }
+    split_h2(h1, hq);
+    split_h2(h1d, hdq);
+  }
+  f32x4 h2[4], h2d[4];
+#pragma unroll
+  for (int bo = 0; bo < 4; ++bo) {
+    phase();
+    Op3 wq;
+    load_w2b(wq, R.w1b, lane, 16 * bo);
+    const f32x4 a2 = CX3 ? w2_block3<false>(hq, wq) : w2_block<false>(hq, wq);
+    const f32x4 a2d = CX3 ? w2_block3<false>(hdq, wq) : w2_block<false>(hdq, wq);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      h2[bo][r] = act_fwd(a2[r]);
+      h2d[bo][r] = act_grad(a2[r]) * a2d[r];
+    }
+  }
+  split_h2(h2, h2q);
+  split_h2(h2d, h2dq);
 }
 
 __device__ __forceinline__ void mlp_pre(const WRes& R, const float* __restrict__ emb, int e0,
@@ -613,13 +658,6 @@ __device__ __forceinline__ int next_block_col(int jj) {
     return fn >= 0 ? L::P[fn].woff : -1;
   }
 }
-// w2r blocks of column block col0 (the last block's f32 dH2 operand, E3GNN_DH2_X3=0): 4 x b128
-__device__ __forceinline__ void load_w2r(f32x4 (&b)[4], __amdgpu_buffer_rsrc_t w2r, int lane, int col0) {
-  const int v = ((lane >> 4) * 16 + (lane & 15)) * 16;
-#pragma unroll
-  for (int bh = 0; bh < 4; ++bh) b[bh] = ldw4(w2r, v, (col0 / 16 * 4 + bh) * 1024);
-}
-
 // channel groups (input irrep I, 16-channel block j) in visiting order
 template <class L>
 constexpr int mul_of(int I) {
@@ -885,76 +923,6 @@ __device__ __forceinline__ void load_gm(float* gmN, __amdgpu_buffer_rsrc_t Rg, i
   constexpr int D3 = 2 * L::P[PN].l3 + 1;
   ldv<4 * D3>(Rg, vg + 4 * g * D3 * 4, (L::P[PN].moff + 16 * jj * D3) * 4, gmN);
 }
-// MLP chain backward of a 16-edge tile from dH2^T (D[hidden 16 bh + 4g + r][edge
-// slot c]): pre-activations recomputed, dA2, dH1^T = W1 dA2^T, demb^T = W0 dA1^T,
-// demb += (rows < 8).  `er`: the edge of the lane's slot c (-1: padded slot).
-__device__ __forceinline__ void mlp_bwd_chain_ids(const WRes& R, const float* __restrict__ emb, int er,
-                                                  int lane, const f32x4 (&dh2)[4],
-                                                  float* __restrict__ demb, const float* dold = nullptr,
-                                                  const float* bk = nullptr, const f32x4* a2k = nullptr) {
-  const int g = lane >> 4;
-  MlpT m;
-  if (a2k) {   // (the tile start's layer-1 pre-activations kept: layer 0 only)
-    const float b[2] = {bk[0], bk[1]};
-    mlp_layer0(R, b, lane, m.a1);
-#pragma unroll
-    for (int bb = 0; bb < 4; ++bb) m.a2[bb] = a2k[bb];
-  } else {
-    float b[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) b[s] = er >= 0 ? emb[(int64_t)er * 8 + 4 * s + g] : 0.f;
-    mlp_chain<CX3>(R, b, lane, m);
-  }
-
-  // dH1^T = W1 dA2^T and demb^T = W0 dA1^T on bf16x6 (operands W1^T and W0^T
-  // pre-split, MlpW::w1tb / w0tb; dA split in their accumulator layout)
-  f32x4 dh1[4];
-  {
-    f32x4 da2[4];
-#pragma unroll
-    for (int bb = 0; bb < 4; ++bb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) da2[bb][r] = dh2[bb][r] * act_grad(m.a2[bb][r]);
-    Op3 dq;
-    split_h2(da2, dq);
-#pragma unroll
-    for (int bi = 0; bi < 4; ++bi) {
-      phase();
-      Op3 wq;
-      load_w2b(wq, R.w1tb, lane, 16 * bi);
-      dh1[bi] = CX3 ? w2_block3<false>(dq, wq) : w2_block<false>(dq, wq);
-    }
-  }
-  f32x4 de;
-  {
-    f32x4 da1[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) da1[q][t] = dh1[q][t] * act_grad(m.a1[q][t]);
-    Op3 dq, wq;
-    split_h2(da1, dq);
-    load_w2b(wq, R.w0tb, lane, 0);
-    de = CX3 ? w2_block3<false>(dq, wq) : w2_block<false>(dq, wq);   // rows 4g + r < 8: the embedding dims
-  }
-  if (g < 2 && er >= 0) {
-    if (dold) {   // (the caller read the old values at the tile start)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) demb[(int64_t)er * 8 + 4 * g + r] = dold[r] + de[r];
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) demb[(int64_t)er * 8 + 4 * g + r] += de[r];
-    }
-  }
-}
-// the same for the CSR edge tile [e0, min(e0 + 16, end))
-__device__ __forceinline__ void mlp_bwd_chain(const WRes& R, const float* __restrict__ emb, int e0,
-                                              int end, int lane, const f32x4 (&dh2)[4],
-                                              float* __restrict__ demb, const float* dold = nullptr,
-                                              const float* bk = nullptr, const f32x4* a2k = nullptr) {
-  const int e = e0 + (lane & 15);
-  mlp_bwd_chain_ids(R, emb, e < end ? e : -1, lane, dh2, demb, dold, bk, a2k);
-}
 
 // Backward of the last block (224 message channels), one wave per NEIGHBOUR
 // node j over its incoming edges (transposed CSR src_ptr / src_perm, ascending
@@ -963,88 +931,24 @@ __device__ __forceinline__ void mlp_bwd_chain(const WRes& R, const float* __rest
 // c]); x = h[j] (one row), the edges' centres' dE/dagg gathered per block
 // (DM = 224 floats a row).  dE/dx[j] is summed over the tile's 16 edge lanes
 // (DPP) once per block, accumulated in LDS and written once (no per-edge
-// buffer, no gather pass); per edge: dE/dY -> dE/du, and dE/dw -> dH2^T = W2
-// dw^T (f32 MFMA) -> MLP chain -> dE/demb.  Every edge is visited once (by its
-// neighbour's wave): deterministic.  The radial weights w of the NEXT visited
-// block are formed (MFMA) before this block's tensor product (VALU).
+// buffer, no gather pass); per edge: dE/dY -> dE/du, and dE/dw . w' summed
+// over the blocks -> dE/dr |radial (drad; w' = W2^T H2'^T, mlp_chain_jvp).
+// Every edge is visited once (by its neighbour's wave): deterministic.  The
+// radial weights w and tangents w' of the NEXT visited block are formed (MFMA,
+// on the one W2 operand block) before this block's tensor product (VALU).
 // Two 16-edge tiles of the node per pass (28 incoming edges on average: one
-// pass per node): every W2 operand block (w recompute and dH2) feeds both
-// tiles, and dE/dx[j] of both tiles is summed in registers before the
-// per-block DPP row sum.  The second tile is skipped when it has no edge.
-// dH2 = dw W2^T (the gradient of the radial MLP's hidden layer; the
-// forward-consistent w = H2 W2 stays on six products) on three bf16 products
-// by default: dw in two pieces (16 significant bits), W2's first two pieces,
-// products p1 q0 + p0 q1 + p0 q0 (dropped terms ~2^-16 of dH2).  Measured on
-// the reference KAT systems: the force errors against the reference are the
-// six-product build's (2.9e-6 .. 2.1e-5 vs 3.1e-6 .. 1.9e-5 eV/A, both
-// dominated by the fp32 path elsewhere; tolerance 1e-4), the middle backward
-// 12 % faster (fewer MFMAs and split instructions).  E3GNN_DH2_X3=0: six.
-#ifndef E3GNN_DH2_X3
-#define E3GNN_DH2_X3 1
-#endif
-// operand pieces are requested before the MFMAs that consume them, not in the
-// per-block interleaved order the compiler chose: the middle backward's pair
-// images from LDS (5.56 -> 5.46 ms per launch, same box) and the last block's
-// dH2 pieces from L2 (2.21 -> 2.10 ms; profiles/r06_s10_*)
-// the middle blocks' tile-end read-modify-writes of dE/du and dE/demb: the
-// old values read at the tile start (5.39 -> 5.34 ms per launch, same box;
-// profiles/r06_s12_*)
-// the middle blocks' tile-start layer-1 pre-activations (a2) and embedding
-// values kept to the tile end, whose MLP chain backward then recomputes layer
-// 0 only (5.38-5.39 -> 5.21-5.27 ms per launch, same box; profiles/r06_s16_*;
-// keeping layer 0's as well measured slower)
-// the same old-value reads for the last block's per-pass dE/du and dE/demb
-// (2.13 -> 2.09-2.12 ms, same box; profiles/r06_s12_*)
-constexpr int LS_PAIR_D = 12288;       // the pair's dH2 operand (w2d: 3 pieces x 4 bh x 1 KB)
-
-// dH2^T += W2[:, pair] dw^T on three bf16 products with the pair's W2 pieces
-// read from global memory (L2: every wave of the launch reads the same
-// operand; w2d order, MlpW::w2d; see dh2_pair for the operand layout), both
-// tiles of a pass at once: each W2 piece block is loaded once and feeds the
-// two tiles' products (per tile it was twice the last block's dH2 operand
-// stream)
-__device__ __forceinline__ void dh2_pair_g2(f32x4 (&dh2)[2][4], const float (&dp)[2][4], const float (&dr)[2][4],
-                                            bool two, __amdgpu_buffer_rsrc_t w2d, int pair, int lane) {
-  bf16x8 d[2][2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    float v[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) v[t] = t < 4 ? dp[u][t] : dr[u][t - 4];
-    split2x8(v, d[u]);
-  }
-  // every piece of the pair requested first (one L2 latency per pair)
-  bf16x8 a[4][2];
-#pragma unroll
-  for (int bh = 0; bh < 4; ++bh)
-#pragma unroll
-    for (int pc = 0; pc < 2; ++pc)
-      a[bh][pc] = __builtin_bit_cast(
-          bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2d, lane * 16, pair * LS_PAIR_D + (pc * 4 + bh) * 1024, 0));
-#pragma unroll
-  for (int bh = 0; bh < 4; ++bh) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (u == 1 && !two) break;
-      dh2[u][bh] = mfma16(a[bh][1], d[u][0], dh2[u][bh]);
-      dh2[u][bh] = mfma16(a[bh][0], d[u][1], dh2[u][bh]);
-      dh2[u][bh] = mfma16(a[bh][0], d[u][0], dh2[u][bh]);
-    }
-  }
-}
-
-// the last block's dH2 on bf16 MFMA from global (L2) W2 pieces: with the
-// three-product form its operand traffic equals the f32 form's (two pieces x 4
-// hidden blocks per pair) and the MFMA cycles drop ~5x (2.60 -> 2.41 ms, same
-// box); the six-product form measured slower than f32, so the six-product
-// build (E3GNN_DH2_X3=0) takes the f32 form there
-constexpr bool NBR_DH2_BF16 = E3GNN_DH2_X3 != 0;
+// pass per node): every W2 operand block feeds both tiles, and dE/dx[j] of
+// both tiles is summed in registers before the per-block DPP row sum.  The
+// second tile is skipped when it has no edge.
+// the pass end's read-modify-writes of dE/du and drad: the old values read at
+// the pass start (for dE/du and the former dE/demb 2.13 -> 2.09-2.12 ms, same
+// box; profiles/r06_s12_*)
 template <class L>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_conv_bwd_nbr(
     const int* __restrict__ src_ptr, const int* __restrict__ src_perm, const int* __restrict__ center,
     const float* __restrict__ emb, const float* __restrict__ Y, const float* __restrict__ h,
     const float* __restrict__ gagg, MlpW W, float* __restrict__ dh, float* __restrict__ dgu, int n_centers,
-    int r_begin, int r_end, float* __restrict__ demb) {
+    int r_begin, int r_end, const float* __restrict__ embd, float* __restrict__ drad) {
   __shared__ __attribute__((aligned(16))) float lds[4][L::DX];
   const int wid = threadIdx.x >> 6;
   const int jn = __builtin_amdgcn_readfirstlane(r_begin + blockIdx.x * 4 + wid);
@@ -1066,9 +970,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     load_w2b(wq, R.w2b, lane, L::P[0].woff);
     int er[2], vg[2];
     float y[2][9];
-    // the pass end's dE/du and dE/demb old values, read here
-    float gu_old[2][3], de_old[2][4];
-    Op3 hq[2];
+    // the pass end's dE/du and drad old values, read here
+    float gu_old[2][3], dr_old[2];
+    Op3 hq[2], hdq[2];   // H2 and its tangent H2'
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int q = q0 + 16 * u + col;
@@ -1078,32 +982,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int k = 0; k < 9; ++k) y[u][k] = er[u] >= 0 ? Y[(int64_t)er[u] * 9 + k] : 0.f;
 #pragma unroll
       for (int k = 0; k < 3; ++k) gu_old[u][k] = (g == 0 && er[u] >= 0) ? dgu[(int64_t)er[u] * 3 + k] : 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) de_old[u][k] = (g < 2 && er[u] >= 0) ? demb[(int64_t)er[u] * 8 + 4 * g + k] : 0.f;
+      dr_old[u] = (g == 0 && er[u] >= 0) ? drad[er[u]] : 0.f;
       if (u == 1 && !two) continue;
-      float b[2];
+      float b[2], bd[2];
 #pragma unroll
-      for (int k = 0; k < 2; ++k) b[k] = er[u] >= 0 ? emb[(int64_t)er[u] * 8 + 4 * k + g] : 0.f;
-      MlpT m;
-      mlp_chain<CX3>(R, b, lane, m);
-      f32x4 h2[4];
-#pragma unroll
-      for (int bb = 0; bb < 4; ++bb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) h2[bb][r] = act_fwd(m.a2[bb][r]);
-      split_h2(h2, hq[u]);
+      for (int k = 0; k < 2; ++k) {
+        b[k] = er[u] >= 0 ? emb[(int64_t)er[u] * 8 + 4 * k + g] : 0.f;
+        bd[k] = er[u] >= 0 ? embd[(int64_t)er[u] * 8 + 4 * k + g] : 0.f;
+      }
+      mlp_chain_jvp(R, b, bd, lane, hq[u], hdq[u]);
     }
-    f32x4 dh2[2][4];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int bb = 0; bb < 4; ++bb) dh2[u][bb] = zero4();
-    float dwp[2][4];   // dE/dw of the block pair's first block, per tile (the bf16 dH2 form)
+    float drl[2] = {0.f, 0.f};   // the lane's share of dE/dw . w' (edge c, channels 4g .. 4g+3 of every block)
     int nb = 0;
     constexpr int NBLK = L::W / 16;
     f32x4 wcur[2], wnxt[2] = {zero4(), zero4()};
+    f32x4 tcur[2], tnxt[2] = {zero4(), zero4()};   // w' of the same blocks
     wcur[0] = w2_block_bwd<false>(hq[0], wq);
+    tcur[0] = w2_block_tan<false>(hdq[0], wq);
     wcur[1] = two ? w2_block_bwd<false>(hq[1], wq) : zero4();
+    tcur[1] = two ? w2_block_tan<false>(hdq[1], wq) : zero4();
     if (NBLK > 1) load_w2b(wq, R.w2v, lane, 16);
     float dYa[2][9];
 #pragma unroll
@@ -1130,19 +1027,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
               float gm[2][4 * D3];
               load_gm<L, pi>(gm[0], Rg, vg[0], g, jj);
               load_gm<L, pi>(gm[1], Rg, vg[1], g, jj);
-              f32x4 bq[4];   // W2 blocks of the f32 dH2 form
-              if constexpr (!NBR_DH2_BF16) load_w2r(bq, R.w2r, lane, p.woff + 16 * jj);
-              f32x4 wv[2] = {wcur[0], wcur[1]};
+              f32x4 wv[2] = {wcur[0], wcur[1]}, tv[2] = {tcur[0], tcur[1]};
               if (nb + 1 < NBLK) {
                 wnxt[0] = w2_block_bwd<false>(hq[0], wq);
+                tnxt[0] = w2_block_tan<false>(hdq[0], wq);
                 wnxt[1] = two ? w2_block_bwd<false>(hq[1], wq) : zero4();
+                tnxt[1] = two ? w2_block_tan<false>(hdq[1], wq) : zero4();
               }
               if (nb + 2 < NBLK) load_w2b(wq, R.w2v, lane, 16 * (nb + 2));
-              float dwr2[2][4];   // both tiles' dE/dw (the bf16 dH2 form)
 #pragma unroll
               for (int u = 0; u < 2; ++u) {
                 if (u == 1 && !two) break;
-                float dwr[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                   phase();
@@ -1150,8 +1045,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                   for (int q = 0; q < 2 * p.l2 + 1; ++q) dy[q] = 0.f;
                   // padded slots: w = 0, g = 0 and y = 0 (so dE/dw = 0)
-                  dwr[r] = tp_bwd_xw<p.l1, p.l2, p.l3>(x + r * D1, y[u] + yoff(p.l2), wv[u][r], gm[u] + r * D3,
-                                                       dx + r * D1, dy);
+                  const float dwr = tp_bwd_xw<p.l1, p.l2, p.l3>(x + r * D1, y[u] + yoff(p.l2), wv[u][r],
+                                                                gm[u] + r * D3, dx + r * D1, dy);
+                  drl[u] += dwr * tv[u][r];   // dE/dw . dw/dr
                   if constexpr (p.l2 > 0) {
 #pragma unroll
                     for (int q = 0; q < 2 * p.l2 + 1; ++q) dYa[u][yoff(p.l2) + q] += dy[q];
@@ -1159,36 +1055,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                   pin<D1>(dx + r * D1);
                   pin<8>(dYa[u] + 1);
                 }
-                if constexpr (NBR_DH2_BF16) {
-#pragma unroll
-                  for (int r = 0; r < 4; ++r) dwr2[u][r] = u == 1 && !two ? 0.f : dwr[r];
-                } else {
-                  // dH2^T += W2[:, block] dw^T: k = lane group g, channel 4g + r
-#pragma unroll
-                  for (int bh = 0; bh < 4; ++bh)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) dh2[u][bh] = mfma(bq[bh][r], dwr[r], dh2[u][bh]);
-                }
-              }
-              if constexpr (NBR_DH2_BF16) {
-                if (!two) {
-#pragma unroll
-                  for (int r = 0; r < 4; ++r) dwr2[1][r] = 0.f;
-                }
-                // dH2^T += W2[:, pair] dw^T over the block pair for both tiles,
-                // each W2 piece loaded once (the pair's first block held in dwp)
-                if (nb & 1) {
-                  dh2_pair_g2(dh2, dwp, dwr2, two, R.w2d, nb >> 1, lane);
-                } else {
-#pragma unroll
-                  for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) dwp[u][r] = dwr2[u][r];
-                }
               }
               pin<4 * D1>(dx);
               wcur[0] = wnxt[0];
               wcur[1] = wnxt[1];
+              tcur[0] = tnxt[0];
+              tcur[1] = tnxt[1];
               ++nb;
             }
           });
@@ -1233,8 +1105,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         o[1] = gu_old[u][1] + gy;
         o[2] = gu_old[u][2] + gz;
       }
-      phase();
-      mlp_bwd_chain_ids(R, emb, er[u], lane, dh2[u], demb, de_old[u]);
+      // dE/dr |radial of edge c: the same sum over the 4 lane groups
+      const float dr = sum_rows4(drl[u]);
+      if (g == 0 && er[u] >= 0) drad[er[u]] = dr_old[u] + dr;
     }
   }
   phase();
@@ -1256,80 +1129,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // W2 operands of each block PAIR: staged once per workgroup in LDS (register
 // staging: issued a whole pair ahead, written between two barriers), so each
 // operand crosses the L2 -> CU path once per 4 tiles instead of once per tile
-// and needs no per-wave prefetch registers.  The backward's dH2 = dw W2^T runs
-// on bf16x6 MFMA over the pair (K = 32 channels): 24 x 16 MFMA cycles instead of
-// 2 x 16 x 32 on f32 MFMA.  Middle blocks: two workgroups per CU (LDS), 2 waves
-// per SIMD (SevenNet-0's: two pairs per barrier, LsQuads); the first block: 3
-// waves per SIMD.
+// and needs no per-wave prefetch registers.  Middle blocks: two workgroups per
+// CU (LDS), 2 waves per SIMD (SevenNet-0's: two pairs per barrier, LsQuads); the
+// first block: 3 waves per SIMD.
 
-// The pair's W2 pieces are staged ONCE, as the [hidden][channel] image of
-// w2_image.h (MlpW::w2s): dH2 reads it by rows, the w recompute transposed
-// (ds_read_b64_tr_b16), each getting the operand registers of the w2d / w2v
-// orders.  The image holds only the pieces the backward's products read: with
-// the three-product forms (E3GNN_BWD_W_X3, E3GNN_DH2_X3) pieces 0 and 1, 8 KB
-// per pair (12 KB when either product runs on six)
+// The pair's W2 pieces are staged as the [hidden][channel] image of
+// w2_image.h (MlpW::w2s) and read transposed (ds_read_b64_tr_b16): the operand
+// registers of the w recompute w^T = W2^T H2^T, which the tangent product
+// w'^T = W2^T H2'^T shares (the image's row reads were the operand of the
+// reverse-mode dH2 = dw W2^T that the tangent replaced).  The image holds only
+// the pieces the two products read: with the three-product forms
+// (E3GNN_BWD_W_X3, E3GNN_DH2_X3) pieces 0 and 1, 8 KB per pair (12 KB when
+// either product runs on six)
 constexpr int LS_WPC = E3GNN_BWD_W_X3 ? 2 : 3;   // pieces the w recompute reads
-constexpr int LS_DPC = E3GNN_DH2_X3 ? 2 : 3;     // pieces dH2 reads
-constexpr int LS_IMG = (LS_WPC > LS_DPC ? LS_WPC : LS_DPC) * w2img::PIECE_BYTES;
+constexpr int LS_DPC = E3GNN_DH2_X3 ? 2 : 3;     // pieces the tangent product reads
+constexpr int LS_PCS = LS_WPC > LS_DPC ? LS_WPC : LS_DPC;   // staged, and read into the shared operand
+constexpr int LS_IMG = LS_PCS * w2img::PIECE_BYTES;
 
-// the w-recompute operand of the pair's block b (transposed reads: every lane
-// of the wave active)
+// the operand of the pair's block b (transposed reads: every lane of the wave
+// active)
 template <int NPC = 3>
 __device__ __forceinline__ void lds_op3(Op3& o, const char* pimg, int b, int lane) {
 #pragma unroll
   for (int pc = 0; pc < NPC; ++pc)
 #pragma unroll
     for (int m = 0; m < 2; ++m) o.v[pc][m] = w2img::tr_read(pimg, lane, b, pc, m);
-}
-
-// dH2^T += W2[:, pair] dw^T on bf16 MFMA (K = 32: element t of lane (g, c) is
-// channel 4g + t of the pair's first block (t < 4) or 4g + t - 4 of its second,
-// the w2d order); A = the W2 pieces (row reads of the LDS image), B = dw split
-// in pieces (three products by default, six with E3GNN_DH2_X3=0)
-__device__ __forceinline__ void dh2_pair(f32x4 (&dh2)[4], const float (&da)[4], const float (&db)[4],
-                                         const char* pimg, int lane) {
-  if constexpr (E3GNN_DH2_X3) {
-    bf16x8 d[2];
-    {
-      float v[8];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) v[t] = t < 4 ? da[t] : db[t - 4];
-      split2x8(v, d);
-    }
-    // every piece read first, fenced from the MFMAs (one exposed LDS latency
-    // for the pair, not one per hidden block)
-    bf16x8 a[4][2];
-#pragma unroll
-    for (int bh = 0; bh < 4; ++bh)
-#pragma unroll
-      for (int pc = 0; pc < 2; ++pc)
-        a[bh][pc] = w2img::row_read(pimg, lane, pc, bh);
-    phase();
-#pragma unroll
-    for (int bh = 0; bh < 4; ++bh) {
-      dh2[bh] = mfma16(a[bh][1], d[0], dh2[bh]);
-      dh2[bh] = mfma16(a[bh][0], d[1], dh2[bh]);
-      dh2[bh] = mfma16(a[bh][0], d[0], dh2[bh]);
-    }
-    return;
-  }
-  bf16x8 d[3];
-  {
-    float v[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) v[t] = t < 4 ? da[t] : db[t - 4];
-    split3x8(v, d);
-  }
-  constexpr int I[6] = {2, 1, 0, 1, 0, 0}, J[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-  for (int bh = 0; bh < 4; ++bh) {
-    bf16x8 a[3];
-#pragma unroll
-    for (int pc = 0; pc < 3; ++pc)
-      a[pc] = w2img::row_read(pimg, lane, pc, bh);
-#pragma unroll
-    for (int q = 0; q < 6; ++q) dh2[bh] = mfma16(a[I[q]], d[J[q]], dh2[bh]);
-  }
 }
 
 // full rounds (64 edges) of a workgroup's edge range: a range re-stages the
@@ -1347,11 +1171,12 @@ constexpr int LS_ROUNDS = 8;
 constexpr int ls_row_stride(int dms) { return dms + ((64 - dms * 4 % 256 + 256) % 256) / 4; }
 
 // Backward of a first / middle block (per-edge dE/dx to dxc, summed per
-// neighbour by the transposed-CSR gather; dE/dY -> dE/du; dE/dw -> dH2 -> MLP
-// chain -> dE/demb), each centre's dE/dagg row staged in LDS once per
-// workgroup range (the four-slot window above).  Same pair
-// structure as the forward (both blocks' w formed at the pair start, next
-// group's neighbour rows prefetched); dH2 of the pair on bf16x6 at its end.
+// neighbour by the transposed-CSR gather; dE/dY -> dE/du; dE/dw . w' summed
+// over the blocks -> dE/dr |radial, drad), each centre's dE/dagg row staged in
+// LDS once per workgroup range (the four-slot window above).  Same pair
+// structure as the forward (both blocks' w and tangents w' formed at the pair
+// start from the same operand registers, next group's neighbour rows
+// prefetched).
 // waves per SIMD: the first block (128 input channels, 1,152 message channels:
 // 34.8 KB of LDS per workgroup, two images) runs three (168 VGPRs with a few
 // spills measured 2.57 -> 2.27 ms against two), the middle blocks two (their
@@ -1416,7 +1241,7 @@ template <class L>
 __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(BwdLsWaves<L>::v, BwdLsWaves<L>::v))) void k_conv_bwd_ls(
     const int* __restrict__ row_ptr, const int* __restrict__ nbr, const float* __restrict__ emb,
     const float* __restrict__ Y, const float* __restrict__ h, const float* __restrict__ gagg, MlpW W,
-    float* __restrict__ dxc, float* __restrict__ dgu, float* __restrict__ demb,
+    float* __restrict__ dxc, float* __restrict__ dgu, const float* __restrict__ embd, float* __restrict__ drad,
     const int* __restrict__ center, int e_begin, int e_end, int c_end, int n_nodes) {
   constexpr int NBLK = L::W / 16, NPAIR = NBLK / 2;
   static_assert(NBLK % 2 == 0, "weight blocks come in pairs");
@@ -1495,12 +1320,9 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
       if constexpr (OFF0 > 0 && Iq == 0) ldv<4>(Rg0, vg0, 16 * jq * 4, g0pf);
     };
     float y[9];
-    // KEEP: old values of the tile end's read-modify-writes, and the tile's
-    // layer-1 pre-activations and embedding values
-    float gu_old[3] = {0.f, 0.f, 0.f}, de_old[4] = {0.f, 0.f, 0.f, 0.f};
-    f32x4 a2k[4];
-    float bk[2];
-    Op3 hq;
+    // KEEP: old values of the tile end's read-modify-writes
+    float gu_old[3] = {0.f, 0.f, 0.f}, dr_old = 0.f;
+    Op3 hq, hdq;   // H2 and its tangent H2' (mlp_chain_jvp)
     // neighbour rows (lanes without an edge read row 0: harmless, their y
     // and w are 0); issued unconditionally, like every vector-memory op
     // between two pair commits, so the commit's wait counts only the staging
@@ -1512,22 +1334,22 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
     const __amdgpu_buffer_rsrc_t Rd =
         rsrc_bytes(dxc ? dxc + (int64_t)(act ? q0 : 0) * L::DX : gagg, (int64_t)nrow * L::DX * 4);
     const int vd = col * L::DX * 4;
-    float b[2];
+    float b[2], bd[2];
     if (act) {
 #pragma unroll
       for (int q = 0; q < 9; ++q) y[q] = er >= 0 ? Y[(int64_t)er * 9 + q] : 0.f;
 #pragma unroll
-      for (int s = 0; s < 2; ++s) b[s] = er >= 0 ? emb[(int64_t)er * 8 + 4 * s + g] : 0.f;
+      for (int s = 0; s < 2; ++s) {
+        b[s] = er >= 0 ? emb[(int64_t)er * 8 + 4 * s + g] : 0.f;
+        bd[s] = er >= 0 ? embd[(int64_t)er * 8 + 4 * s + g] : 0.f;
+      }
       if constexpr (KEEP) {
-        // the tile end's read-modify-writes (dE/du, dE/demb of the lane's
+        // the tile end's read-modify-writes (dE/du, drad of the lane's
         // edge): old values read here, their latency under the whole tile
         if (g == 0 && er >= 0) {
 #pragma unroll
           for (int k = 0; k < 3; ++k) gu_old[k] = dgu[(int64_t)er * 3 + k];
-        }
-        if (g < 2 && er >= 0) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) de_old[k] = demb[(int64_t)er * 8 + 4 * g + k];
+          dr_old = drad[er];
         }
       }
     }
@@ -1553,29 +1375,14 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
           reinterpret_cast<f32x4*>(smem + ((cs0 + i / NRK) & 3) * RS)[k] = rowv[i];
       }
     }
-    if (act) {
-      MlpT m;
-      mlp_chain<CX3>(R, b, lane, m);
-      if constexpr (KEEP) {
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) a2k[bb] = m.a2[bb];
-        bk[0] = b[0];
-        bk[1] = b[1];
-      }
-      f32x4 h2[4];
-#pragma unroll
-      for (int bb = 0; bb < 4; ++bb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) h2[bb][r] = act_fwd(m.a2[bb][r]);
-      split_h2(h2, hq);
-    }
-    if constexpr (STAMPED) STAMP(1);   // tile setup: edge loads, MLP chain, H2 split
-    f32x4 dh2[4] = {zero4(), zero4(), zero4(), zero4()};
+    if (act) mlp_chain_jvp(R, b, bd, lane, hq, hdq);
+    if constexpr (STAMPED) STAMP(1);   // tile setup: edge loads, MLP chain and tangent, H2 / H2' splits
+    float drl = 0.f;   // the lane's share of dE/dw . w' (edge c, channels 4g .. 4g+3 of every block)
     float dYa[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) dYa[q] = 0.f;
-    float dwp[4];   // dE/dw of the pair's first block
     f32x4 wv0 = zero4(), wv1 = zero4();   // w of the pair's two blocks
+    f32x4 tv0 = zero4(), tv1 = zero4();   // and their tangents w'
     sfor<3>([&](auto I) {
       constexpr int MUL = iblock_mul<L, I>();
       if constexpr (MUL > 0) {
@@ -1633,20 +1440,23 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
                   if constexpr (STAMPED) STAMP(2);   // barriers + staging
                 }
                 if constexpr (!ODD) {
+                  if constexpr (STAMPED && POS != 0) STAMP(5);   // tensor product (+ stores)
                   if (act) {
                     ls_prio<1>();   // MFMA bursts first
                     Op3 wq, wq1;   // both blocks' pieces read first
-                    lds_op3<LS_WPC>(wq, pimg, 0, lane);
-                    lds_op3<LS_WPC>(wq1, pimg, 1, lane);
+                    lds_op3<LS_PCS>(wq, pimg, 0, lane);
+                    lds_op3<LS_PCS>(wq1, pimg, 1, lane);
                     phase();
                     wv0 = w2_block_bwd<false>(hq, wq);
+                    tv0 = w2_block_tan<false>(hdq, wq);
                     wv1 = w2_block_bwd<false>(hq, wq1);
+                    tv1 = w2_block_tan<false>(hdq, wq1);
                     ls_prio<0>();
                   }
-                  if constexpr (STAMPED) STAMP(3);   // w recompute
+                  if constexpr (STAMPED) STAMP(3);   // w recompute and tangent
                 }
                 if (act) {
-                  const f32x4 wv = ODD ? wv1 : wv0;
+                  const f32x4 wv = ODD ? wv1 : wv0, tv = ODD ? tv1 : tv0;
                   float gm[4 * D3];
                   if constexpr (OFF0 > 0 && pi == 0) {   // (two images: from L2, prefetched)
 #pragma unroll
@@ -1661,16 +1471,8 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
                   tp_bwd_xw4<p.l1, p.l2, p.l3>(x, y + yoff(p.l2), wv, gm, dx, dYa + yoff(p.l2), dwr);
                   if constexpr (L::KIND != 0) pin<4 * D1>(dx);
                   pin<8>(dYa + 1);
-                  if constexpr (ODD) {
-                    if constexpr (STAMPED) STAMP(5);   // tensor product (+ stores)
-                    ls_prio<1>();   // MFMA bursts first
-                    dh2_pair(dh2, dwp, dwr, pimg, lane);
-                    ls_prio<0>();
-                    if constexpr (STAMPED) STAMP(4);   // dH2 (split + MFMA)
-                  } else {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) dwp[r] = dwr[r];
-                  }
+                  for (int r = 0; r < 4; ++r) drl += dwr[r] * tv[r];   // dE/dw . dw/dr
                 }
                 if constexpr (TWO && POS == 2 * NIMG - 1) rb ^= 1;   // the next pair(s) read the other buffer
               }
@@ -1693,6 +1495,7 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
         }
       }
     });
+    if constexpr (STAMPED) STAMP(5);   // (the last block's tensor product)
     if (act) {
       // dE/dY of edge c: sum over the 4 lane groups, then dE/du through the SH
       // polynomials (serial_code.py:50-70)
@@ -1725,11 +1528,14 @@ __global__ __launch_bounds__(64 * LS_WPG) __attribute__((amdgpu_waves_per_eu(Bwd
           o[2] += gz;
         }
       }
-      if constexpr (STAMPED) STAMP(5);
-      mlp_bwd_chain(R, emb, q0, end, lane, dh2, demb, KEEP ? de_old : nullptr, KEEP ? bk : nullptr,
-                    KEEP ? a2k : nullptr);
+      // dE/dr |radial of edge c: the same sum over the 4 lane groups
+      const float dr = sum_rows4(drl);
+      if (g == 0 && er >= 0) {
+        if constexpr (KEEP) drad[er] = dr_old + dr;
+        else drad[er] += dr;
+      }
     }
-    if constexpr (STAMPED) STAMP(6);   // tile end: dE/dY sums, MLP chain backward
+    if constexpr (STAMPED) STAMP(6);   // tile end: dE/dY and dE/dr sums
   }
   if constexpr (STAMPED) STAMP_FLUSH(blockIdx.x * WPG + wid);
 }
@@ -1741,7 +1547,7 @@ static hipError_t bwd_ls_impl(const FusedArgs& a, hipStream_t s) {
   const int ne = a.e_end - a.e_begin, per = LS_ROUNDS * 16 * LS_WPG;   // edges per workgroup
   if (ne <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_conv_bwd_ls<L>, dim3((ne + per - 1) / per), dim3(64 * LS_WPG), 0, s, a.row_ptr, a.nbr,
-                     a.emb, a.Y, a.h, a.gagg, a.W, a.dxc, a.dgu, a.demb, a.center, a.e_begin, a.e_end,
+                     a.emb, a.Y, a.h, a.gagg, a.W, a.dxc, a.dgu, a.embd, a.drad, a.center, a.e_begin, a.e_end,
                      a.c_end, a.n_nodes);
   return hipGetLastError();
 }
@@ -1760,7 +1566,7 @@ static hipError_t bwd_nbr_impl(const FusedArgs& a, hipStream_t s) {
   const int nn = a.node_end - a.node_begin;
   hipLaunchKernelGGL(k_conv_bwd_nbr<L>, dim3((nn + 3) / 4), dim3(256), 0, s, a.src_ptr, a.src_perm,
                      a.center, a.emb, a.Y, a.h, a.gagg, a.W, a.dh, a.dgu, a.n_centers, a.node_begin,
-                     a.node_end, a.demb);
+                     a.node_end, a.embd, a.drad);
   return hipGetLastError();
 }
 

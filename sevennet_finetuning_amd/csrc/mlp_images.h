@@ -33,7 +33,7 @@ inline void bf16_pieces(float v, uint16_t (&p)[3]) {
 // w2b (MlpW::w2b): a = p0 + p1 + p2 exactly (bf16 pieces, round to
 // nearest even); element t of lane (g, c) in k-half m of column block cb
 // is a[16(2m + t/4) + 4g + t%4][16 cb + c].  a: [64][N] (N a multiple of 16);
-// also the order of w1b, w1tb and w0tb.
+// also the order of w1b.
 inline std::vector<float> pack_w2b(const std::vector<float>& a, int N) {
   std::vector<float> o((size_t)N * 64 * 3 / 2);
   uint16_t* oh = reinterpret_cast<uint16_t*>(o.data());
@@ -50,7 +50,10 @@ inline std::vector<float> pack_w2b(const std::vector<float>& a, int N) {
   return o;
 }
 
-// w2d (MlpW::w2d): element t of lane (g, c) for hidden block bh is
+// w2d, the order the pair image's ROW reads give (w2_image.h row_read; no
+// kernel reads it since the fused backward takes the radial derivative in
+// forward mode, the microtest still checks the image against it): element t
+// of lane (g, c) for hidden block bh is
 // w2[16 bh + c][col], col = cols[2P] + 4g + t (t < 4) or cols[2P + 1] + 4g + t - 4.
 // a2: [64][W]; cols: the visited 16-column blocks' starts, two per pair P.
 inline std::vector<float> pack_w2d(const std::vector<float>& a2, int W, const std::vector<int>& cols) {
@@ -78,21 +81,6 @@ inline std::vector<float> pack_w2v(const std::vector<float>& b2, const std::vect
   for (size_t k = 0; k < cols.size(); ++k)
     std::memcpy(v2.data() + k * blk, b2.data() + (size_t)(cols[k] / 16) * blk, blk * 4);
   return v2;
-}
-
-// w2r (MlpW::w2r), f32: per column block cb and hidden block bh, lane (g, c)
-// holds w2[16 bh + c][16 cb + 4g + r], r = 0..3 (channel 4g + r: the fused
-// backward's dE/dw layout)
-inline std::vector<float> pack_w2r(const std::vector<float>& a2, int W) {
-  std::vector<float> r2((size_t)W * 64);
-  for (int cb = 0; cb < W / 16; ++cb)
-    for (int bh = 0; bh < 4; ++bh)
-      for (int g = 0; g < 4; ++g)
-        for (int c = 0; c < 16; ++c)
-          for (int r = 0; r < 4; ++r)
-            r2[((size_t)(cb * 4 + bh) * 64 + g * 16 + c) * 4 + r] =
-                a2[(size_t)(16 * bh + c) * W + 16 * cb + 4 * g + r];
-  return r2;
 }
 
 // The bf16x6 operand image of one k_nodelin_b block (gemm.hip): w = [K1 + K2][N]

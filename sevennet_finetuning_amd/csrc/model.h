@@ -88,12 +88,10 @@ struct e3gnn_model {
   struct Mlp {
     using DBuf = e3gnn::DBuf;
     DBuf w0, w1, w2, w0t, w1t, w2t;  // f32, plain and transposed (w1, w2 and the transposes: the v1 path)
-    DBuf w2r;            // f32 operand order of the E3GNN_DH2_X3=0 backward (fused.h)
     DBuf w2b;            // 3-way bf16 split of w2 in 16x16x32 operand order (fused.h)
-    DBuf w2d;            // the same for the last block's backward pairs (fused.h)
     DBuf w2v;            // w2b's column blocks in visiting order (last block; fused.h)
     DBuf w2s;            // the lock-step backward's pair images (first / middle; w2_image.h)
-    DBuf w1b, w1tb, w0tb;  // layer-1 / chain-backward operands, w2b order (fused.h)
+    DBuf w1b;            // layer 1's operand, w2b order (fused.h)
   };
   std::vector<Mlp> mlp;
   // any other nequip-family deployment: the generic engine (generic.cpp)

@@ -153,8 +153,8 @@ std::vector<PathDef> kind_paths(int code) {
 
 // Column start of every 16-channel weight block in the order the fused
 // kernels visit them (input irrep I, channel block jj, then the paths of I in
-// instruction order): pairs of consecutive blocks form one K = 32 MFMA operand
-// of the lock-step backward's dH2 product (MlpW::w2d).
+// instruction order): pairs of consecutive blocks share one staged image of
+// the lock-step backward (MlpW::w2s).
 std::vector<int> bwd_w_block_cols(int code) {
   const auto P = kind_paths(code);
   std::vector<int> cols;
@@ -555,40 +555,31 @@ void load_block_mlp(e3gnn_model* m, const Deploy& D, int t) {
   must_upload(mm.w0t, scaled(w0, 8, 64, s0, true), "upload mlp");
   must_upload(mm.w1t, a1t, "upload mlp");
   must_upload(mm.w2t, scaled(w2, 64, W, s2, true), "upload mlp");
-  // the MLP's other products in w2b's order: W1 (64 x 64, in x out), W1^T,
-  // and W0^T (64 x 8) padded to 16 columns
-  {
-    std::vector<float> a0t((size_t)64 * 16, 0.f);
-    for (int n = 0; n < 8; ++n)
-      for (int k = 0; k < 64; ++k) a0t[(size_t)k * 16 + n] = a0[(size_t)n * 64 + k];
-    must_upload(mm.w1b, mlpimg::pack_w2b(a1, 64), "upload mlp (w1b)");
-    must_upload(mm.w1tb, mlpimg::pack_w2b(a1t, 64), "upload mlp (w1b)");
-    must_upload(mm.w0tb, mlpimg::pack_w2b(a0t, 16), "upload mlp (w1b)");
-  }
+  // layer 1 in w2b's order: W1 (64 x 64, in x out), the operand of the value
+  // and of the backward's tangent alike
+  must_upload(mm.w1b, mlpimg::pack_w2b(a1, 64), "upload mlp (w1b)");
   // the kernels' visiting order of the 16-column blocks (input irrep,
   // channel block, path): pairs of consecutive blocks
   const std::vector<int> cols = bwd_w_block_cols(m->kcode(t));
   if ((int)cols.size() * 16 != W || cols.size() % 2)
     throw std::runtime_error("dE/dw block order does not cover the weights");
   const std::vector<float> b2 = mlpimg::pack_w2b(a2, W);
-  // the last block's backward (k_conv_bwd_nbr) reads its operands from
-  // L2 in the lane orders w2d and w2v; the first and middle blocks'
-  // (k_conv_bwd_ls) stage one image per pair that serves both (w2s)
+  // the last block's backward (k_conv_bwd_nbr) reads its operand from L2
+  // in the lane order w2v; the first and middle blocks' (k_conv_bwd_ls)
+  // stage one image per pair (w2s)
   if (m->kcode(t) % 3 == 2) {
-    must_upload(mm.w2d, mlpimg::pack_w2d(a2, W, cols), "upload mlp (w2d)");
     must_upload(mm.w2v, mlpimg::pack_w2v(b2, cols), "upload mlp (w2v)");
   } else {
     // w2s (MlpW::w2s): per pair P and piece, the [hidden unit][channel]
     // matrix of the pair's 2 x 16 columns cols[2P], cols[2P + 1] in the
     // swizzled order of w2_image.h, the same residual chain of bf16
-    // pieces: read by rows it gives w2d's lane registers, read
-    // transposed (ds_read_b64_tr_b16) w2v's
+    // pieces: read transposed (ds_read_b64_tr_b16) it gives w2v's lane
+    // registers
     const size_t npairs = cols.size() / 2;
     std::vector<float> s2(npairs * w2img::PAIR_BYTES / 4);
     w2img::pack(a2.data(), W, cols.data(), (int)npairs, reinterpret_cast<uint16_t*>(s2.data()));
     must_upload(mm.w2s, s2, "upload mlp (w2s)");
   }
-  must_upload(mm.w2r, mlpimg::pack_w2r(a2, W), "upload mlp (packed)");
   must_upload(mm.w2b, b2, "upload mlp (packed)");
   trace_point("load:mlp");
 }

@@ -4,8 +4,9 @@
 #include <cstdint>
 
 namespace e3gnn {
+// embd (nullable): d emb / dr [E, 8], the tangent input of the fused backward
 hipError_t launch_edge_embed(int64_t E, const float* vec, const float* coeffs, float rc, float ron,
-                             int raw_sh, float* Y, float* emb, hipStream_t s);
+                             int raw_sh, float* Y, float* emb, float* embd, hipStream_t s);
 // the fine-tune step's edge-geometry tangent / coefficient gradient (node.hip)
 hipError_t launch_edge_geom_jvp(int64_t E, const float* vec, const float* coeffs, float rc, float ron,
                                 int raw_sh, const int* center, const int* nbr, const int64_t* batch,
@@ -15,9 +16,11 @@ hipError_t launch_edge_geom_coeff(int64_t E, const float* vec, const float* coef
                                   float ron, const float* embb, const float* embdb, const float* rd,
                                   float* out, hipStream_t s);
 int edge_force_blocks(int64_t E);
+// the radial part of dE/dr from demb ([E, 8] dE/demb, through d emb / dr) and
+// drad ([E] dE/dr itself, the fused kernels'), either nullable; vir_part nullable
 hipError_t launch_edge_force(int64_t E, const float* vec, const float* coeffs, float rc, float ron,
-                             int raw_sh, const float* dY, const float* dgu, const float* demb, float* fe,
-                             float* vir_part, hipStream_t s);  // vir_part nullable
+                             int raw_sh, const float* dY, const float* dgu, const float* demb,
+                             const float* drad, float* fe, float* vir_part, hipStream_t s);
 hipError_t launch_atom_force(int n_nodes, int n_centers, const int* row_ptr, const int* src_ptr,
                              const int* src_perm, const float* fe, float* F, hipStream_t s);
 hipError_t launch_build_graph(int64_t E, int n_centers, int n_nodes, const int* center,

@@ -23,9 +23,31 @@ inline int nblk(int64_t n, int t = TPB) { return (int)((n + t - 1) / t); }
 // 'component'; polynomial of serial_code.py:50-70) of the unit vector
 // (normalize=True) or, for checkpoints before sevenn 0.9 (`_normalize_sph`
 // absent, util.py:130-146), of the raw vector: Y_l(r) = |r|^l Y_l(r/|r|).
+// XPLOR envelope and its r-derivative (edge_embedding.py:163-173)
+__device__ __forceinline__ void xplor(float r, float rc, float ron, float& env, float& denv) {
+  env = 1.f;
+  denv = 0.f;
+  if (r >= ron) {
+    const float rc2 = rc * rc, r2 = r * r, ron2 = ron * ron;
+    const float a = rc2 - r2, d = rc2 - ron2, d3 = d * d * d;
+    env = a * a * (rc2 + 2.f * r2 - 3.f * ron2) / d3;
+    denv = 12.f * r * a * (ron2 - r2) / d3;
+  }
+}
+// d emb_n / dr of emb_n = B_n(r) env(r): the one form k_edge_embed (embd, the
+// fused backward's tangent input) and k_edge_force (the chain rule from
+// dE/demb) both use
+__device__ __forceinline__ float emb_dr(float cn, float r, float rc, float env, float denv) {
+  const float sn = sinf(cn * r), cs = cosf(cn * r);
+  const float b = (2.f / rc) * sn / r;
+  const float db = (2.f / rc) * (cn * cs * r - sn) / (r * r);
+  return db * env + b * denv;
+}
+
+// embd (nullable): d emb / dr, [E, 8]
 __global__ void k_edge_embed(int64_t E, const float* __restrict__ vec, const float* __restrict__ coeffs,
                              float rc, float ron, int raw_sh, float* __restrict__ Y,
-                             float* __restrict__ emb) {
+                             float* __restrict__ emb, float* __restrict__ embd) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= E) return;
   const float vx = vec[3 * e], vy = vec[3 * e + 1], vz = vec[3 * e + 2];
@@ -42,15 +64,15 @@ __global__ void k_edge_embed(int64_t E, const float* __restrict__ vec, const flo
   yo[6] = s5 * (y * y - 0.5f * (x * x + z * z));
   yo[7] = s5 * (s3 * y * z);
   yo[8] = s5 * (0.5f * s3 * (z * z - x * x));
-  float env = 1.f;
-  if (r >= ron) {
-    const float rc2 = rc * rc, r2 = r * r, ron2 = ron * ron;
-    const float a = rc2 - r2, d = rc2 - ron2;
-    env = a * a * (rc2 + 2.f * r2 - 3.f * ron2) / (d * d * d);
-  }
+  float env, denv;
+  xplor(r, rc, ron, env, denv);
   float* eo = emb + 8 * e;
 #pragma unroll
   for (int n = 0; n < 8; ++n) eo[n] = (2.f / rc) * sinf(coeffs[n] * r) / r * env;
+  if (embd) {
+#pragma unroll
+    for (int n = 0; n < 8; ++n) embd[8 * e + n] = emb_dr(coeffs[n], r, rc, env, denv);
+  }
 }
 
 // dE/dr_ij from the accumulated dE/dY (all layers) and dE/demb (all layers):
@@ -62,7 +84,8 @@ __global__ void k_edge_embed(int64_t E, const float* __restrict__ vec, const flo
 __global__ void k_edge_force(int64_t E, const float* __restrict__ vec, const float* __restrict__ coeffs,
                              float rc, float ron, int raw_sh, const float* __restrict__ dY,
                              const float* __restrict__ dgu, const float* __restrict__ demb,
-                             float* __restrict__ fe, float* __restrict__ vir_part) {
+                             const float* __restrict__ drad, float* __restrict__ fe,
+                             float* __restrict__ vir_part) {
   __shared__ float red[6][TPB];
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   float v6[6] = {0, 0, 0, 0, 0, 0};
@@ -91,23 +114,15 @@ __global__ void k_edge_force(int64_t E, const float* __restrict__ vec, const flo
       fy = (gy - dot * uy) / r;
       fz = (gz - dot * uz) / r;
     }
-    // radial part
-    float env = 1.f, denv = 0.f;
-    if (r >= ron) {
-      const float rc2 = rc * rc, r2 = r * r, ron2 = ron * ron;
-      const float a = rc2 - r2, d = rc2 - ron2, d3 = d * d * d;
-      env = a * a * (rc2 + 2.f * r2 - 3.f * ron2) / d3;
-      denv = 12.f * r * a * (ron2 - r2) / d3;
-    }
-    const float* ge = demb + 8 * e;
-    float dr = 0.f;
+    // radial part: dE/dr taken by the fused kernels in forward mode (drad),
+    // or dE/demb (the v1 kernels, the fine-tune step) through d emb / dr
+    float dr = drad ? drad[e] : 0.f;
+    if (demb) {
+      float env, denv;
+      xplor(r, rc, ron, env, denv);
+      const float* ge = demb + 8 * e;
 #pragma unroll
-    for (int n = 0; n < 8; ++n) {
-      const float cn = coeffs[n];
-      const float sn = sinf(cn * r), cs = cosf(cn * r);
-      const float b = (2.f / rc) * sn / r;
-      const float db = (2.f / rc) * (cn * cs * r - sn) / (r * r);
-      dr += ge[n] * (db * env + b * denv);
+      for (int n = 0; n < 8; ++n) dr += ge[n] * emb_dr(coeffs[n], r, rc, env, denv);
     }
     fx += dr * ux;
     fy += dr * uy;
@@ -135,18 +150,6 @@ __global__ void k_edge_force(int64_t E, const float* __restrict__ vec, const flo
     __syncthreads();
   }
   if (threadIdx.x < 6) vir_part[(int64_t)blockIdx.x * 6 + threadIdx.x] = red[threadIdx.x][0];
-}
-
-// XPLOR envelope and its r-derivative (edge_embedding.py:163-173)
-__device__ __forceinline__ void xplor(float r, float rc, float ron, float& env, float& denv) {
-  env = 1.f;
-  denv = 0.f;
-  if (r >= ron) {
-    const float rc2 = rc * rc, r2 = r * r, ron2 = ron * ron;
-    const float a = rc2 - r2, d = rc2 - ron2, d3 = d * d * d;
-    env = a * a * (rc2 + 2.f * r2 - 3.f * ron2) / d3;
-    denv = 12.f * r * a * (ron2 - r2) / d3;
-  }
 }
 
 // Tangent of the edge geometry for the fine-tune step's reverse-over-forward
@@ -914,8 +917,8 @@ __global__ void k_unpack(int64_t n, int dim, const int* __restrict__ idx, const 
   } while (0)
 
 hipError_t launch_edge_embed(int64_t E, const float* vec, const float* coeffs, float rc, float ron,
-                             int raw_sh, float* Y, float* emb, hipStream_t s) {
-  LAUNCH(k_edge_embed, nblk(E), E, vec, coeffs, rc, ron, raw_sh, Y, emb);
+                             int raw_sh, float* Y, float* emb, float* embd, hipStream_t s) {
+  LAUNCH(k_edge_embed, nblk(E), E, vec, coeffs, rc, ron, raw_sh, Y, emb, embd);
   return hipGetLastError();
 }
 hipError_t launch_edge_geom_jvp(int64_t E, const float* vec, const float* coeffs, float rc, float ron,
@@ -936,9 +939,9 @@ hipError_t launch_edge_geom_coeff(int64_t E, const float* vec, const float* coef
 }
 int edge_force_blocks(int64_t E) { return nblk(E); }
 hipError_t launch_edge_force(int64_t E, const float* vec, const float* coeffs, float rc, float ron,
-                             int raw_sh, const float* dY, const float* dgu, const float* demb, float* fe,
-                             float* vir_part, hipStream_t s) {
-  LAUNCH(k_edge_force, nblk(E), E, vec, coeffs, rc, ron, raw_sh, dY, dgu, demb, fe, vir_part);
+                             int raw_sh, const float* dY, const float* dgu, const float* demb,
+                             const float* drad, float* fe, float* vir_part, hipStream_t s) {
+  LAUNCH(k_edge_force, nblk(E), E, vec, coeffs, rc, ron, raw_sh, dY, dgu, demb, drad, fe, vir_part);
   return hipGetLastError();
 }
 hipError_t launch_atom_force(int n_nodes, int n_centers, const int* row_ptr, const int* src_ptr,

@@ -3,7 +3,10 @@
 // MFMA operands, so a pair is staged in LDS once instead of as a matrix and
 // its transpose.
 //   * read by rows (ds_read_b64) it is the A operand of dH2 = W2[:, pair] dw^T
-//     (rows = hidden units, K = the pair's 32 channels; the former w2d order);
+//     (rows = hidden units, K = the pair's 32 channels; the former w2d order).
+//     No kernel takes this read any more: the fused backward forms the radial
+//     derivative in forward mode from the transposed reads alone (fused.hip
+//     w2_block_tan); row_read stays for the microtest that pins the layout;
 //   * read transposed (ds_read_b64_tr_b16) it is the A operand of the w
 //     recompute w^T = W2^T H2^T (rows = channels, K = hidden units; the former
 //     w2v order).

@@ -26,7 +26,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PHASES = ['tile start', 'setup+MLP chain', 'barriers+staging', 'w recompute', 'dH2',
+# (slot 4 was the reverse-mode dH2 product; the forward-mode tangent is formed
+# with the w recompute and stamps nothing there)
+PHASES = ['tile start', 'setup+MLP chain+tangent', 'barriers+staging', 'w recompute+tangent', '(dH2: retired)',
           'TP (+dxc stores)', 'tile end', 'TOTAL']
 # a variant built with E3GNN_STAMPS_FWD=1 stamps the middle FORWARD instead
 PHASES_FWD = ['pass start', 'setup+MLP chain', 'w MFMAs', 'tensor product', 'path start (rows)',
@@ -64,7 +66,7 @@ def main():
         tiles = (int(box['center'].numel()) + 15) // 16
         print(f'tiles >= {tiles} (edges / 16), wave cycles per tile <= {tot / tiles:.0f}')
     for k in range(7):
-        print(f'  {names[k]:18s} {a[:, k].sum() / tot:6.3f}   {a[:, k].mean():10.0f} cyc/wave')
+        print(f'  {names[k]:24s} {a[:, k].sum() / tot:6.3f}   {a[:, k].mean():10.0f} cyc/wave')
     print(f'  unaccounted        {1 - a[:, :7].sum() / tot:6.3f}')
     del _lib
 
