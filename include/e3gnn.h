@@ -632,6 +632,40 @@ int e3gnn_plist_build(e3gnn_plist* h, const double* x, double cutoff, int64_t* n
                       void* stream);
 int e3gnn_plist_fetch(e3gnn_plist* h, int32_t* edge_center, int32_t* edge_nbr, float* edge_vec,
                       void* stream);
+/* The rank graph of the parallel pair style (ParallelStep::build's loop,
+ * pair_e3gnn_parallel.cpp:285-325) from the same kind of list, on the same
+ * handle.  atom_class int32 [n_total] replaces atom_row: the row in [0, n) of
+ * an owned atom and of every ghost that carries an owned atom's tag (a periodic
+ * self-image), and n + k for a ghost whose tag the rank does not own, k in
+ * [0, n_class) numbering those tags in any order (the output does not depend
+ * on the numbering).  Rows [0, n) are the list rows; edges are in list order
+ * with edge_vec as above; a class n + k with at least one edge gets the row
+ * n + r, r its rank among such classes by the index of their first edge --
+ * the host loop's first-seen rows; n_ghost counts them, and ghost_atom[r] is
+ * the atom index j of that first edge (the first-seen image).
+ * e3gnn_plist_set_rank is e3gnn_plist_set with these rules on top of the list
+ * rules: n_class in [0, n_total - n], fewer than 2^31 candidates, atom_class in
+ * [0, n + n_class), atom_class[row_atom[t]] = t, every class of [n, n +
+ * n_class) named by an atom; E3GNN_ERR_ARG naming the atom, row or class.
+ * e3gnn_plist_check_rank_list is that check alone (host only, no device).
+ * e3gnn_plist_rank_build (any number of times after one set_rank; x as for
+ * _build) returns *n_edges and *n_ghost after one synchronise of `stream`.
+ * e3gnn_plist_rank_fetch writes the edges and ghost_atom int32 [n_ghost] to
+ * DEVICE memory the caller sized (no synchronise).  Integer atomics only (a
+ * minimum and a count): every output is bitwise reproducible.
+ * The handle holds one list: a set of either kind replaces it (the other
+ * kind's build is then "before set"), and a build call of one kind ends the
+ * other kind's fetch.  The argument rules are checked before any HIP call. */
+int e3gnn_plist_check_rank_list(int64_t n, int64_t n_total, const int32_t* row_atom,
+                                const int64_t* cand_ptr, const int32_t* cand, int32_t neighmask,
+                                const int32_t* atom_class, int64_t n_class);
+int e3gnn_plist_set_rank(e3gnn_plist* h, int64_t n, int64_t n_total, const int32_t* row_atom,
+                         const int64_t* cand_ptr, const int32_t* cand, int32_t neighmask,
+                         const int32_t* atom_class, int64_t n_class, void* stream);
+int e3gnn_plist_rank_build(e3gnn_plist* h, const double* x, double cutoff, int64_t* n_edges,
+                           int64_t* n_ghost, void* stream);
+int e3gnn_plist_rank_fetch(e3gnn_plist* h, int32_t* edge_center, int32_t* edge_nbr, float* edge_vec,
+                           int32_t* ghost_atom, void* stream);
 
 /* ---- device-resident training dataset and batch assembly ----
  * Replaces the host side of the reference's training input: the graph list of

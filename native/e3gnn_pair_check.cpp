@@ -33,9 +33,19 @@
 // reuse_edges_changed and reuse_bits_equal.  --time K runs style (1) only and
 // prints, per mode (host; device with the list re-uploaded; device with the
 // list reused), the median and range of K alternating compute() times in ms.
+// With --parallel-graph-device style (2) runs again on the requested grid in
+// both graph modes (pair_style e3gnn/parallel graph host|device) on the same
+// atoms and lists, and the line gains the object parallel_graph_device: per
+// rank edges / edges_host, ghost_rows / ghost_rows_host and reuse_edges;
+// graph_bits_equal (memcmp of center, nbr, vec, type and the row -> atom map,
+// rank by rank), energy_, forces_ and virial_bits_equal, comm_equal (the comm
+// counters of both modes), repeat_bitwise, and the reuse leg of --graph-device
+// as reuse_edges_changed and reuse_bits_equal.  With --time K it runs style
+// (2) only, the ranks as threads sharing one GPU, and prints rank 0's times of
+// build() + comm_preprocess + compute() per mode in the same alternation.
 //
 //   e3gnn_pair_check <model dir> <structure> <px> <py> <pz> [seed] [--gpu-aware] [--vatom]
-//                    [--graph-device] [--time K]
+//                    [--graph-device] [--parallel-graph-device] [--time K]
 //   structure: si:<cells> (displaced Si diamond) or a file
 //              "n \n 9 cell values (rows = lattice vectors) \n symbol x y z ..."
 #include <hip/hip_runtime.h>
@@ -420,6 +430,25 @@ std::string graph_device_keys(const Structure& S, const std::string& dir, unsign
   return buf;
 }
 
+// median and range, and the rounds themselves, of a --time series as JSON
+std::string stats(std::vector<double> v) {
+  std::sort(v.begin(), v.end());
+  const size_t m = v.size();
+  const double med = m % 2 ? v[m / 2] : 0.5 * (v[m / 2 - 1] + v[m / 2]);
+  char buf[96];
+  std::snprintf(buf, sizeof(buf), "{\"median\": %.3f, \"min\": %.3f, \"max\": %.3f}", med, v.front(), v.back());
+  return std::string(buf);
+}
+std::string rounds(const std::vector<double>& v) {
+  std::string s = "[";
+  char buf[32];
+  for (size_t k = 0; k < v.size(); ++k) {
+    std::snprintf(buf, sizeof(buf), "%s%.3f", k ? ", " : "", v[k]);
+    s += buf;
+  }
+  return s + "]";
+}
+
 // --time K: style (1) only; per round host mode, device mode with the list
 // re-uploaded (ago = 0), device mode with the list reused (ago = 1)
 int time_graph_modes(const Structure& S, const std::string& dir, int K) {
@@ -446,23 +475,6 @@ int time_graph_modes(const Structure& S, const std::string& dir, int K) {
     t[2].push_back(timed(1));
     wins += t[2].back() < t[0].back();
   }
-  auto stats = [](std::vector<double> v) {
-    std::sort(v.begin(), v.end());
-    const size_t m = v.size();
-    const double med = m % 2 ? v[m / 2] : 0.5 * (v[m / 2 - 1] + v[m / 2]);
-    char buf[96];
-    std::snprintf(buf, sizeof(buf), "{\"median\": %.3f, \"min\": %.3f, \"max\": %.3f}", med, v.front(), v.back());
-    return std::string(buf);
-  };
-  auto rounds = [](const std::vector<double>& v) {
-    std::string s = "[";
-    char buf[32];
-    for (size_t k = 0; k < v.size(); ++k) {
-      std::snprintf(buf, sizeof(buf), "%s%.3f", k ? ", " : "", v[k]);
-      s += buf;
-    }
-    return s + "]";
-  };
   std::printf("{\"n_atoms\": %d, \"ghosts\": %d, \"edges\": %lld, \"rounds\": %d, \"host_ms\": %s, "
               "\"device_new_list_ms\": %s, \"device_reused_list_ms\": %s, \"reused_beats_host_rounds\": %d, "
               "\"host_rounds_ms\": %s, \"device_new_list_rounds_ms\": %s, \"device_reused_list_rounds_ms\": %s}\n",
@@ -471,23 +483,280 @@ int time_graph_modes(const Structure& S, const std::string& dir, int K) {
   return 0;
 }
 
+// Style (2) on one emulated rank, kept alive between force evaluations
+// (--parallel-graph-device): the setup of run_rank, one borders() and one list
+// build, then compute() as often as the caller likes, in either graph mode.
+// Every rank of the grid runs the same sequence (the exchanges meet in World).
+struct ParallelRig {
+  LAMMPS lmp;
+  Memory mem;
+  Error err;
+  Atom atom;
+  Neighbor neigh;
+  Force force;
+  Domain dom;
+  std::unique_ptr<CommBrick> comm;
+  std::unique_ptr<PairE3GNNParallel> pair;
+  NeighList list;
+  struct Result {
+    double energy = 0, virial[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<double> f;   // owned atoms, after the reverse communication
+    long long edges = 0, ghost_rows = 0;
+    std::vector<int32_t> center, nbr, type;
+    std::vector<float> vec;
+    std::vector<int> row_atom;
+    e3gnn_pair::CommMaps::Stats st;
+    bool same_bits(const Result& o) const {
+      return !std::memcmp(&energy, &o.energy, 8) && !std::memcmp(virial, o.virial, 48) &&
+             f.size() == o.f.size() && !std::memcmp(f.data(), o.f.data(), f.size() * 8);
+    }
+    bool same_graph(const Result& o) const {
+      auto eq = [](const auto& a, const auto& b) {
+        return a.size() == b.size() && !std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0]));
+      };
+      return eq(center, o.center) && eq(nbr, o.nbr) && eq(vec, o.vec) && eq(type, o.type) &&
+             eq(row_atom, o.row_atom);
+    }
+    bool same_comm(const Result& o) const {
+      return st.swaps == o.st.swaps && st.sent == o.st.sent && st.relayed == o.st.relayed &&
+             st.extra_rows == o.st.extra_rows && st.zero_sends == o.st.zero_sends &&
+             st.trash_forward == o.st.trash_forward && st.trash_reverse == o.st.trash_reverse;
+    }
+  };
+
+  ParallelRig(const Structure& S, const std::string& model_dir, const int grid[3], int me, World* world,
+              std::mutex* load_mutex) {
+    lmp.memory = &mem;
+    lmp.error = &err;
+    lmp.atom = &atom;
+    lmp.neighbor = &neigh;
+    lmp.force = &force;
+    lmp.domain = &dom;
+    comm.reset(new CommBrick(&lmp, world, me, grid));
+    lmp.comm = comm.get();
+    dom.set_cell(S.cell);
+    neigh.skin = SKIN;
+    for (int a = 0; a < S.n; ++a) {
+      double s[3], x[3];
+      dom.x2lamda(&S.pos[3 * a], s);
+      bool mine = true;
+      for (int d = 0; d < 3; ++d) {
+        s[d] -= std::floor(s[d]);
+        if (s[d] >= 1.0) s[d] -= 1.0;
+        const int c = std::min(grid[d] - 1, (int)(s[d] * grid[d]));
+        mine = mine && c == comm->myloc[d];
+      }
+      if (!mine) continue;
+      dom.lamda2x(s, x);
+      atom.add(x, s, S.tag[a], S.type[a]);
+    }
+    atom.nlocal = (int)atom.tags.size();
+    atom.natoms = S.n;
+    atom.ntypes = (int)S.elements.size();
+    atom.sync();
+    std::vector<std::string> args = {"*", "*", "4", model_dir};
+    for (const auto& e : S.elements) args.push_back(e);
+    std::vector<char*> argv;
+    for (auto& a : args) argv.push_back(&a[0]);
+    {
+      std::lock_guard<std::mutex> lk(*load_mutex);
+      pair.reset(new PairE3GNNParallel(&lmp));
+      pair->settings(0, nullptr);
+      pair->coeff((int)argv.size(), argv.data());
+    }
+    pair->init_style();
+    const double cut = pair->init_one(1, 1);
+    comm->setup(cut + SKIN);
+    comm->borders();
+    neigh.build_full(&atom, cut, &list);
+    pair->init_list(0, &list);
+  }
+  void graph(const char* where) {
+    std::string a = "graph", b = where;
+    char* argv[2] = {&a[0], &b[0]};
+    pair->settings(2, argv);
+  }
+  // build() + comm_preprocess + compute(), without the ghost forces' way home
+  void step(int ago) {
+    neigh.ago = ago;
+    std::fill(atom.fs.begin(), atom.fs.end(), 0.0);
+    pair->compute(1 | 2, 1);
+  }
+  Result compute(int ago) {
+    step(ago);
+    comm->reverse_comm();   // ghost forces onto their owners (newton on)
+    Result r;
+    r.energy = pair->eng_vdwl;
+    std::copy(pair->virial, pair->virial + 6, r.virial);
+    r.f.assign(atom.fs.begin(), atom.fs.begin() + 3 * (size_t)atom.nlocal);
+    e3gnn_pair::ParallelStep* core = pair->core();
+    r.edges = core->nedges();
+    r.ghost_rows = core->graph_size() - core->nlocal();
+    if (core->graph_copy(r.center, r.nbr, r.vec, r.type, r.row_atom)) throw std::runtime_error(core->error());
+    r.st = pair->comm_maps()->stats();
+    return r;
+  }
+  void displace(unsigned seed, double amp) {
+    const int nt = atom.nlocal + atom.nghost;
+    for (int a = 0; a < nt; ++a) {
+      std::mt19937 r(seed * 7919u + (unsigned)atom.tag[a]);
+      std::uniform_real_distribution<double> u(-amp, amp);
+      for (int k = 0; k < 3; ++k) atom.x[a][k] += u(r);
+    }
+  }
+};
+
+// one thread per rank of the grid, each with a rig of its own; `body(rig, rank)`
+template <class Body>
+void on_ranks(const Structure& S, const std::string& dir, const int grid[3], Body body) {
+  const int P = grid[0] * grid[1] * grid[2];
+  World world(P);
+  std::mutex load_mutex;
+  std::vector<std::string> errs(P);
+  std::vector<std::thread> th;
+  for (int r = 0; r < P; ++r)
+    th.emplace_back([&, r] {
+      try {
+        if (hipSetDevice(0) != hipSuccess) throw std::runtime_error("hipSetDevice");
+        ParallelRig rig(S, dir, grid, r, &world, &load_mutex);
+        body(rig, r);
+      } catch (const std::exception& e) {
+        errs[r] = e.what();
+        world.abort();
+      }
+    });
+  for (auto& t : th) t.join();
+  for (int r = 0; r < P; ++r)
+    if (!errs[r].empty() && errs[r] != "world aborted")
+      throw std::runtime_error("rank " + std::to_string(r) + ": " + errs[r]);
+}
+
+// --parallel-graph-device: the keys of the "parallel_graph_device" object
+std::string parallel_graph_device_keys(const Structure& S, const std::string& dir, const int grid[3],
+                                       unsigned seed) {
+  const int P = grid[0] * grid[1] * grid[2];
+  struct Out {
+    long long edges = 0, edges_host = 0, ghost_rows = 0, ghost_rows_host = 0, reuse_edges = 0;
+    bool graph = false, energy = false, forces = false, virial = false, comm = false, repeat = false,
+         reuse_changed = false, reuse = false;
+  };
+  std::vector<Out> outs(P);
+  on_ranks(S, dir, grid, [&](ParallelRig& rig, int r) {
+    const auto host = rig.compute(0);
+    rig.graph("device");
+    const auto dev = rig.compute(0), dev2 = rig.compute(0);
+    // reuse leg: the atoms move, the list stays (ago = 1); device first, so
+    // that the step really reuses the list uploaded above
+    rig.displace(seed, 0.4);
+    const auto rdev = rig.compute(1);
+    rig.graph("host");
+    const auto rhost = rig.compute(1);
+    Out& o = outs[r];
+    o.edges = dev.edges;
+    o.edges_host = host.edges;
+    o.ghost_rows = dev.ghost_rows;
+    o.ghost_rows_host = host.ghost_rows;
+    o.reuse_edges = rdev.edges;
+    o.graph = dev.same_graph(host);
+    o.energy = !std::memcmp(&dev.energy, &host.energy, 8);
+    o.forces = dev.f.size() == host.f.size() && !std::memcmp(dev.f.data(), host.f.data(), dev.f.size() * 8);
+    o.virial = !std::memcmp(dev.virial, host.virial, 48);
+    o.comm = dev.same_comm(host) && rdev.same_comm(rhost);
+    o.repeat = dev.same_bits(dev2) && dev.same_graph(dev2);
+    o.reuse_changed = rdev.edges != dev.edges || !rdev.same_graph(dev);
+    o.reuse = rdev.same_bits(rhost) && rdev.same_graph(rhost);
+  });
+  auto tf = [](bool b) { return b ? "true" : "false"; };
+  auto all = [&](bool Out::*m) {
+    bool b = true;
+    for (const Out& o : outs) b = b && o.*m;
+    return b;
+  };
+  auto list = [&](long long Out::*m) {
+    std::string s = "[";
+    for (int r = 0; r < P; ++r) s += (r ? ", " : "") + std::to_string(outs[r].*m);
+    return s + "]";
+  };
+  bool reuse_changed = false;   // on any rank: a small brick may keep its count
+  for (const Out& o : outs) reuse_changed = reuse_changed || o.reuse_changed;
+  return ", \"parallel_graph_device\": {\"edges\": " + list(&Out::edges) + ", \"edges_host\": " +
+         list(&Out::edges_host) + ", \"ghost_rows\": " + list(&Out::ghost_rows) +
+         ", \"ghost_rows_host\": " + list(&Out::ghost_rows_host) + ", \"graph_bits_equal\": " +
+         tf(all(&Out::graph)) + ", \"energy_bits_equal\": " + tf(all(&Out::energy)) +
+         ", \"forces_bits_equal\": " + tf(all(&Out::forces)) + ", \"virial_bits_equal\": " +
+         tf(all(&Out::virial)) + ", \"comm_equal\": " + tf(all(&Out::comm)) + ", \"repeat_bitwise\": " +
+         tf(all(&Out::repeat)) + ", \"reuse_edges\": " + list(&Out::reuse_edges) +
+         ", \"reuse_edges_changed\": " + tf(reuse_changed) + ", \"reuse_bits_equal\": " +
+         tf(all(&Out::reuse)) + "}";
+}
+
+// --parallel-graph-device --time K: style (2) on the grid, the ranks threads
+// of this process sharing one GPU; rank 0's wall time of build() +
+// comm_preprocess + compute() per round in host mode, device mode with the
+// list re-uploaded (ago = 0) and device mode with the list reused (ago = 1)
+int time_parallel_graph_modes(const Structure& S, const std::string& dir, const int grid[3], int K) {
+  using clk = std::chrono::steady_clock;
+  std::vector<double> t[3];
+  int wins = 0, nghost = 0, nlocal = 0;
+  long long edges = 0, ghost_rows = 0;
+  on_ranks(S, dir, grid, [&](ParallelRig& rig, int r) {
+    auto timed = [&](int ago) {
+      const auto t0 = clk::now();
+      rig.step(ago);   // ends in a stream synchronise
+      return std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    };
+    for (int w = 0; w < 2; ++w) timed(0);
+    rig.graph("device");
+    for (int w = 0; w < 2; ++w) timed(0);
+    for (int w = 0; w < 2; ++w) timed(1);
+    for (int k = 0; k < K; ++k) {
+      rig.graph("host");
+      const double a = timed(0);
+      rig.graph("device");
+      const double b = timed(0), c = timed(1);
+      if (r == 0) {
+        t[0].push_back(a);
+        t[1].push_back(b);
+        t[2].push_back(c);
+        wins += c < a;
+      }
+    }
+    if (r == 0) {
+      nlocal = rig.atom.nlocal;
+      nghost = rig.atom.nghost;
+      edges = rig.pair->core()->nedges();
+      ghost_rows = rig.pair->core()->graph_size() - rig.pair->core()->nlocal();
+    }
+  });
+  std::printf("{\"style\": \"e3gnn/parallel\", \"n_atoms\": %d, \"ranks_as_threads_on_one_gpu\": %d, "
+              "\"rank0_owned\": %d, \"rank0_ghosts\": %d, \"rank0_edges\": %lld, \"rank0_ghost_rows\": %lld, "
+              "\"rounds\": %d, \"host_ms\": %s, \"device_new_list_ms\": %s, \"device_reused_list_ms\": %s, "
+              "\"reused_beats_host_rounds\": %d, \"host_rounds_ms\": %s, \"device_new_list_rounds_ms\": %s, "
+              "\"device_reused_list_rounds_ms\": %s}\n",
+              S.n, grid[0] * grid[1] * grid[2], nlocal, nghost, edges, ghost_rows, K, stats(t[0]).c_str(),
+              stats(t[1]).c_str(), stats(t[2]).c_str(), wins, rounds(t[0]).c_str(), rounds(t[1]).c_str(),
+              rounds(t[2]).c_str());
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc < 6) {
     std::fprintf(stderr, "usage: %s model_dir structure px py pz [seed] [--gpu-aware] [--vatom] "
-                         "[--graph-device] [--time K]\n", argv[0]);
+                         "[--graph-device] [--parallel-graph-device] [--time K]\n", argv[0]);
     return 2;
   }
   const std::string dir = argv[1];
   const int grid[3] = {std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5])};
   unsigned seed = 0;
-  bool want_vatom = false, want_graph_device = false;
+  bool want_vatom = false, want_graph_device = false, want_parallel_graph_device = false;
   int time_rounds = 0;
   for (int k = 6; k < argc; ++k) {
     if (!std::strcmp(argv[k], "--gpu-aware")) setenv("E3GNN_GPU_AWARE_MPI", "1", 1);
     else if (!std::strcmp(argv[k], "--vatom")) want_vatom = true;
     else if (!std::strcmp(argv[k], "--graph-device")) want_graph_device = true;
+    else if (!std::strcmp(argv[k], "--parallel-graph-device")) want_parallel_graph_device = true;
     else if (!std::strcmp(argv[k], "--time") && k + 1 < argc) time_rounds = std::max(1, std::atoi(argv[++k]));
     else seed = (unsigned)std::atoi(argv[k]);
   }
@@ -496,6 +765,7 @@ int main(int argc, char** argv) {
     const Structure S = load_structure(argv[2], rng);
     if (time_rounds) {
       if (hipSetDevice(0) != hipSuccess) throw std::runtime_error("hipSetDevice");
+      if (want_parallel_graph_device) return time_parallel_graph_modes(S, dir, grid, time_rounds);
       return time_graph_modes(S, dir, time_rounds);
     }
     e3gnn_pair::Model model(dir, 0);
@@ -599,7 +869,8 @@ int main(int argc, char** argv) {
       return buf;
     };
     const std::string vs = vatom_keys(ser), vp = vatom_keys(par);
-    const std::string gd = want_graph_device ? graph_device_keys(S, dir, seed) : "";
+    std::string gd = want_graph_device ? graph_device_keys(S, dir, seed) : "";
+    if (want_parallel_graph_device) gd += parallel_graph_device_keys(S, dir, grid, seed);
     std::printf(
         "{\"n_atoms\": %d, \"ranks\": %d, \"energy_ref\": %.8f, \"max_virial_ref\": %.6e, "
         "\"serial\": {\"energy\": %.8f, \"energy_rel\": %.3e, \"max_force\": %.3e, \"max_virial\": %.3e, "

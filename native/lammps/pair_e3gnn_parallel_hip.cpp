@@ -106,6 +106,8 @@ void PairE3GNNParallel::compute(int eflag, int vflag)
   nv.nlocal = atom->nlocal;
   nv.nghost = atom->nghost;
   nv.neighmask = NEIGHMASK;
+  nv.list_age = neighbor->ago;   // 0 on the step the list was rebuilt
+  nv.x_flat = atom->x[0];        // Atom's x is one contiguous block (memory->create)
   // graph: local rows in list order, ghosts within the cutoff deduplicated by tag
   if (step->build(nv, species, atom->natoms)) error->one(FLERR, "e3gnn/parallel: " + step->error());
   comm_preprocess();
@@ -214,9 +216,16 @@ void PairE3GNNParallel::allocate()
   memory->create(cutsq, n + 1, n + 1, "pair:cutsq");
 }
 
-void PairE3GNNParallel::settings(int narg, char ** /*arg*/)
+// pair_style e3gnn/parallel [graph host|device]: where the rank graph is built
+// (e3gnn_pair::ParallelStep::GraphBuild; host when absent)
+void PairE3GNNParallel::settings(int narg, char **arg)
 {
-  if (narg != 0) error->all(FLERR, "Illegal pair_style command");
+  if (narg == 0) graph_device = 0;
+  else if (narg == 2 && strcmp(arg[0], "graph") == 0 && strcmp(arg[1], "host") == 0) graph_device = 0;
+  else if (narg == 2 && strcmp(arg[0], "graph") == 0 && strcmp(arg[1], "device") == 0) graph_device = 1;
+  else error->all(FLERR, "Illegal pair_style command");
+  if (step) step->set_graph_build(graph_device ? e3gnn_pair::ParallelStep::GraphBuild::Device
+                                               : e3gnn_pair::ParallelStep::GraphBuild::Host);
 }
 
 // pair_coeff * * <n segments> <deployment dir> <element per type>: the
@@ -238,6 +247,7 @@ void PairE3GNNParallel::coeff(int narg, char **arg)
     model.reset(new e3gnn_pair::Model(arg[3], device));
     species = model->type_map(elements);
     step.reset(new e3gnn_pair::ParallelStep(*model));
+    if (graph_device) step->set_graph_build(e3gnn_pair::ParallelStep::GraphBuild::Device);
     maps.reset(new e3gnn_pair::CommMaps(*step));
   } catch (const std::exception &e) {
     error->all(FLERR, std::string("e3gnn/parallel: ") + e.what());

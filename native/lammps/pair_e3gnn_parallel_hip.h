@@ -7,8 +7,12 @@
    segment API of libe3gnn_hip.so through native/pair_e3gnn_core.  One deployment
    directory serves every segment:
 
-     pair_style e3gnn/parallel
+     pair_style e3gnn/parallel [graph host|device]
      pair_coeff * * <n segments (ignored)> <deployment dir> <element per type>
+
+   graph device builds each rank's graph on the GPU from LAMMPS' list
+   (e3gnn_pair::ParallelStep::GraphBuild), bit for bit the host loop's; host
+   is the default.
 
    Build: this header as src/pair_e3gnn_parallel.h (the name the CommBrick patch
    includes) with pair_e3gnn_parallel_hip.cpp, pair_e3gnn_core.{h,cpp},
@@ -63,6 +67,9 @@ class PairE3GNNParallel : public Pair {
 
   // the per-swap row maps of the last compute (counters for tests and logs)
   const e3gnn_pair::CommMaps *comm_maps() const { return maps.get(); }
+  // the step of the last compute (its graph, for tests and logs)
+  e3gnn_pair::ParallelStep *core() const { return step.get(); }
+  int graph_device = 0;   // pair_style e3gnn/parallel graph device
   bool print_info = false;
   int world_rank = 0;
 

@@ -357,11 +357,20 @@ ParallelStep::ParallelStep(const Model& model) : model_(model) {
 ParallelStep::~ParallelStep() {
   g_.release();
   if (comm_) (void)hipFree(comm_);
+  if (x_dev_) (void)hipFree(x_dev_);
+  if (ghost_dev_) (void)hipFree(ghost_dev_);
+  if (plist_) e3gnn_plist_free(plist_);
   if (stream_) (void)hipStreamDestroy((hipStream_t)stream_);
   if (ctx_) e3gnn_ctx_free(ctx_);
 }
 
+void ParallelStep::set_graph_build(GraphBuild g) {
+  if (g != build_) list_valid_ = false;
+  build_ = g;
+}
+
 int ParallelStep::build(const NeighborView& nv, const std::vector<int>& map, int64_t natoms) {
+  if (build_ == GraphBuild::Device) return build_device(nv, map, natoms);
   const int nl = nv.inum;
   const double rc2 = model_.cutoff() * model_.cutoff();
   nlocal_ = nl;
@@ -434,8 +443,189 @@ int ParallelStep::build(const NeighborView& nv, const std::vector<int>& map, int
   }
   for (size_t r = 0; r < row_to_i_.size(); ++r) i_to_row_[row_to_i_[r]] = (int)r;
   nghost_graph_ = (int64_t)row_to_i_.size() - nl;
+  nedges_ = (int64_t)center_.size();
   CORE_ABI(e3gnn_graph_set(ctx_, nl, nghost_graph_, (int64_t)center_.size(), type_.data(),
                            center_.data(), nbr_.data(), vec_.data(), stream_));
+  return E3GNN_OK;
+}
+
+// The same graph from the same list on the device (e3gnn_plist_set_rank /
+// _rank_build / _rank_fetch): rows in list order, a row's candidates in the
+// list's order, ghost rows in the order of their first edge.  When the list is
+// new the flattened list and the class of every atom travel; x every step, and
+// the first-seen atom of every ghost row comes back to fill the row maps.
+int ParallelStep::build_device(const NeighborView& nv, const std::vector<int>& map, int64_t natoms) {
+  const int nl = nv.inum;
+  const int64_t ntot = (int64_t)nv.nlocal + nv.nghost;
+  hipStream_t s = (hipStream_t)stream_;
+  nlocal_ = nl;
+  tag_ = nv.tag;
+  ntotal_ = ntot;
+  tag_to_row_.assign(natoms + 1, -1);
+  tag_to_extra_.assign(natoms + 1, -1);
+  i_to_row_.assign(ntotal_, -1);
+  row_to_i_.clear();
+  type_.clear();
+  nextra_ = 0;
+  ntrash_ = 0;
+  auto type_of = [&](int i, int32_t& out) {
+    const int ty = nv.type[i];
+    if (ty < 1 || ty >= (int)map.size() || map[ty] < 0) return false;
+    out = map[ty];
+    return true;
+  };
+  // local rows in list order, as in build()
+  for (int ii = 0; ii < nl; ++ii) {
+    const int i = nv.ilist[ii];
+    const int64_t tg = nv.tag[i];
+    if (tg < 1 || tg > natoms) {
+      err_ = "atom tag out of range";
+      return E3GNN_ERR_ARG;
+    }
+    tag_to_row_[tg] = ii;
+    row_to_i_.push_back(i);
+    int32_t sp;
+    if (!type_of(i, sp)) {
+      err_ = "atom type without a pair_coeff element";
+      return E3GNN_ERR_ARG;
+    }
+    type_.push_back(sp);
+  }
+  if (!plist_) {
+    int dev = 0;
+    CORE_HIP(hipGetDevice(&dev));
+    plist_ = e3gnn_plist_create(dev);
+    if (!plist_) {
+      err_ = std::string("e3gnn_plist_create: ") + e3gnn_last_error();
+      return E3GNN_ERR_ARG;
+    }
+  }
+  const bool fresh = !list_valid_ || nv.list_age == 0 || nv.inum != up_inum_ ||
+                     nv.nlocal != up_nlocal_ || nv.nghost != up_nghost_ ||
+                     (const void*)nv.firstneigh != up_first_;
+  if (fresh) {
+    list_valid_ = false;
+    // every atom's tag and type now: the kernel cannot refuse one later (the
+    // host loop looks at a ghost only once it is inside the cutoff)
+    for (int64_t a = 0; a < ntot; ++a) {
+      int32_t sp;
+      if (nv.tag[a] < 1 || nv.tag[a] > natoms) {
+        err_ = "neighbour tag out of range";
+        return E3GNN_ERR_ARG;
+      }
+      if (!type_of((int)a, sp)) {
+        err_ = "atom type without a pair_coeff element";
+        return E3GNN_ERR_ARG;
+      }
+    }
+    cand_ptr_.resize((size_t)nl + 1);
+    cand_ptr_[0] = 0;
+    for (int ii = 0; ii < nl; ++ii) cand_ptr_[ii + 1] = cand_ptr_[ii] + nv.numneigh[nv.ilist[ii]];
+    cand_.resize((size_t)cand_ptr_[nl] + 1);   // + 1: never a null pointer
+    for (int ii = 0; ii < nl; ++ii) {
+      const int i = nv.ilist[ii];
+      if (nv.numneigh[i] > 0)
+        std::memcpy(&cand_[cand_ptr_[ii]], nv.firstneigh[i], (size_t)nv.numneigh[i] * sizeof(int));
+    }
+    // classes: the row of an atom whose tag has a local row (the atom itself
+    // or a periodic self-image), else nl + k, k numbering the other tags as
+    // the atoms come.  Any dense numbering would do: the ghost rows follow
+    // the order of the first edges, never the class ids
+    atom_class_.resize((size_t)ntot);
+    tag_class_.assign(natoms + 1, -1);
+    int32_t nclass = 0;
+    for (int64_t a = 0; a < ntot; ++a) {
+      const int64_t tg = nv.tag[a];
+      if (tag_to_row_[tg] >= 0) {
+        atom_class_[a] = tag_to_row_[tg];
+      } else {
+        if (tag_class_[tg] < 0) tag_class_[tg] = nl + nclass++;
+        atom_class_[a] = tag_class_[tg];
+      }
+    }
+    CORE_ABI(e3gnn_plist_set_rank(plist_, nl, ntot, nv.ilist, cand_ptr_.data(), cand_.data(),
+                                  nv.neighmask, atom_class_.data(), nclass, s));
+    up_inum_ = nv.inum;
+    up_nlocal_ = nv.nlocal;
+    up_nghost_ = nv.nghost;
+    up_first_ = (const void*)nv.firstneigh;
+    list_valid_ = true;
+  }
+  if (ntot > x_cap_) {
+    if (x_dev_) CORE_HIP(hipFree(x_dev_));
+    x_dev_ = nullptr;
+    x_cap_ = ntot + ntot / 5 + 64;
+    CORE_HIP(hipMalloc(&x_dev_, (size_t)x_cap_ * 24));
+  }
+  const double* xh = nv.x_flat;
+  if (!xh) {
+    xpack_.resize(3 * (size_t)ntot);
+    for (int64_t a = 0; a < ntot; ++a) std::memcpy(&xpack_[3 * (size_t)a], nv.x[a], 24);
+    xh = xpack_.data();
+  }
+  CORE_HIP(hipMemcpyAsync(x_dev_, xh, (size_t)ntot * 24, hipMemcpyHostToDevice, s));
+  int64_t ng = 0;
+  CORE_ABI(e3gnn_plist_rank_build(plist_, x_dev_, model_.cutoff(), &nedges_, &ng, s));
+  try {
+    g_.reserve(nl + ng, nedges_);
+  } catch (const std::exception& e) {
+    err_ = e.what();
+    return E3GNN_ERR_HIP;
+  }
+  if (ng > ghost_cap_) {
+    if (ghost_dev_) CORE_HIP(hipFree(ghost_dev_));
+    ghost_dev_ = nullptr;
+    ghost_cap_ = ng + ng / 5 + 64;
+    CORE_HIP(hipMalloc(&ghost_dev_, (size_t)ghost_cap_ * 4));
+  }
+  CORE_ABI(e3gnn_plist_rank_fetch(plist_, g_.center, g_.nbr, g_.vec, ghost_dev_, s));
+  ghost_atom_.resize((size_t)ng);
+  if (ng) CORE_HIP(hipMemcpyAsync(ghost_atom_.data(), ghost_dev_, (size_t)ng * 4, hipMemcpyDeviceToHost, s));
+  CORE_HIP(hipStreamSynchronize(s));
+  // ghost rows: the first-seen image of each tag, as the host loop keeps it
+  for (int64_t r = 0; r < ng; ++r) {
+    const int j = ghost_atom_[r];
+    if (nv.tag[j] < 1 || nv.tag[j] > natoms) {   // checked when the list was new
+      err_ = "neighbour tag out of range";
+      return E3GNN_ERR_ARG;
+    }
+    tag_to_row_[nv.tag[j]] = nl + (int)r;
+    row_to_i_.push_back(j);
+    int32_t sp = 0;
+    if (!type_of(j, sp)) {
+      err_ = "atom type without a pair_coeff element";
+      return E3GNN_ERR_ARG;
+    }
+    type_.push_back(sp);
+  }
+  for (size_t r = 0; r < row_to_i_.size(); ++r) i_to_row_[row_to_i_[r]] = (int)r;
+  nghost_graph_ = ng;
+  // device edges, host types: e3gnn_graph_set copies each array with
+  // hipMemcpyDefault, so the two kinds of pointer mix
+  CORE_ABI(e3gnn_graph_set(ctx_, nl, nghost_graph_, nedges_, type_.data(), g_.center, g_.nbr, g_.vec,
+                           stream_));
+  return E3GNN_OK;
+}
+
+int ParallelStep::graph_copy(std::vector<int32_t>& center, std::vector<int32_t>& nbr,
+                             std::vector<float>& vec, std::vector<int32_t>& type,
+                             std::vector<int>& row_atom) {
+  type = type_;
+  row_atom = row_to_i_;
+  if (build_ == GraphBuild::Host) {
+    center = center_;
+    nbr = nbr_;
+    vec = vec_;
+    return E3GNN_OK;
+  }
+  center.resize((size_t)nedges_);
+  nbr.resize((size_t)nedges_);
+  vec.resize(3 * (size_t)nedges_);
+  if (nedges_) {
+    CORE_HIP(hipMemcpy(center.data(), g_.center, (size_t)nedges_ * 4, hipMemcpyDeviceToHost));
+    CORE_HIP(hipMemcpy(nbr.data(), g_.nbr, (size_t)nedges_ * 4, hipMemcpyDeviceToHost));
+    CORE_HIP(hipMemcpy(vec.data(), g_.vec, (size_t)nedges_ * 12, hipMemcpyDeviceToHost));
+  }
   return E3GNN_OK;
 }
 

@@ -149,8 +149,21 @@ class SerialStep {
 // exchange itself belongs to the host (LAMMPS CommBrick through
 // pack/unpack_*_comm_gnn, row maps in CommMaps below): the step exposes the row
 // buffer `comm_rows()` = [graph rows | extra rows | zero row | trash rows].
+//
+// The graph is built on the host (GraphBuild::Host, the default: the
+// reference's loop) or on the device (GraphBuild::Device: e3gnn_plist_set_rank
+// / _rank_build / _rank_fetch walk the same list in the same order and give the
+// ghosts their first-seen rows, so the graph, the row maps and every result are
+// bitwise those of the host loop).  On the device the list travels only when
+// it is new, by SerialStep's rule; the steps in between upload x and download
+// the first-seen atom of every ghost row.  One difference: when the list is
+// new the device mode checks the tag and the type of every owned and ghost
+// atom, the host loop those of a ghost only once it is inside the cutoff.
 class ParallelStep {
  public:
+  enum class GraphBuild { Host, Device };
+  void set_graph_build(GraphBuild g);
+  GraphBuild graph_build() const { return build_; }
   // the host's exchange: called once per layer boundary (forward) and once
   // per backward layer boundary (reverse)
   struct Exchange {
@@ -177,7 +190,12 @@ class ParallelStep {
   int graph_size() const { return (int)row_to_i_.size(); }
   int extra_rows() const { return nextra_; }
   int64_t nlocal() const { return nlocal_; }
-  int64_t nedges() const { return (int64_t)center_.size(); }
+  int64_t nedges() const { return nedges_; }
+  // the graph of the last build on the host, in either mode (tests and
+  // e3gnn_pair_check: the device mode downloads it); row_atom = graph row ->
+  // LAMMPS atom index
+  int graph_copy(std::vector<int32_t>& center, std::vector<int32_t>& nbr, std::vector<float>& vec,
+                 std::vector<int32_t>& type, std::vector<int>& row_atom);
   // row buffer of the current exchange on the device, width comm_dim() floats
   float* comm_rows() const { return comm_; }
   int comm_dim() const { return comm_dim_; }
@@ -219,6 +237,22 @@ class ParallelStep {
   int64_t comm_cap_ = 0;
   int comm_dim_ = 0, comm_nrows_ = 0;
   std::string err_;
+  int64_t nedges_ = 0;
+  // build() in GraphBuild::Device
+  int build_device(const NeighborView& nv, const std::vector<int>& map, int64_t natoms);
+  // GraphBuild::Device: the list filter, the flattened list with its classes
+  // and what the last upload was made from
+  GraphBuild build_ = GraphBuild::Host;
+  e3gnn_plist* plist_ = nullptr;
+  bool list_valid_ = false;
+  int up_inum_ = -1, up_nlocal_ = -1, up_nghost_ = -1;
+  const void* up_first_ = nullptr;
+  std::vector<int64_t> cand_ptr_;
+  std::vector<int32_t> cand_, atom_class_, tag_class_, ghost_atom_;
+  std::vector<double> xpack_;
+  double* x_dev_ = nullptr;
+  int32_t* ghost_dev_ = nullptr;
+  int64_t x_cap_ = 0, ghost_cap_ = 0;
 };
 
 // The per-swap row maps of CommBrick's GNN exchange, LAMMPS-free: what

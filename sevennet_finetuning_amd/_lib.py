@@ -117,6 +117,14 @@ SIGNATURES = {
                                  _P(ctypes.c_int32), ctypes.c_int32, _P(ctypes.c_int32), _vp]),
     'e3gnn_plist_build': (_c_int, [_vp, _vp, ctypes.c_double, _P(_c_i64), _vp]),
     'e3gnn_plist_fetch': (_c_int, [_vp, _vp, _vp, _vp, _vp]),
+    'e3gnn_plist_check_rank_list': (_c_int, [_c_i64, _c_i64, _P(ctypes.c_int32), _P(_c_i64),
+                                             _P(ctypes.c_int32), ctypes.c_int32, _P(ctypes.c_int32),
+                                             _c_i64]),
+    'e3gnn_plist_set_rank': (_c_int, [_vp, _c_i64, _c_i64, _P(ctypes.c_int32), _P(_c_i64),
+                                      _P(ctypes.c_int32), ctypes.c_int32, _P(ctypes.c_int32), _c_i64,
+                                      _vp]),
+    'e3gnn_plist_rank_build': (_c_int, [_vp, _vp, ctypes.c_double, _P(_c_i64), _P(_c_i64), _vp]),
+    'e3gnn_plist_rank_fetch': (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     'e3gnn_dataset_create': (_vp, [_c_int, _c_i64, _P(_c_i64), _P(_c_i64), _vp]),
     'e3gnn_dataset_free': (None, [_vp]),
     'e3gnn_dataset_collate': (_c_int, [_vp, _c_i64, _P(_c_i64), _c_int, _c_i64, _c_i64, _c_i64,

@@ -309,7 +309,12 @@ class ListFilter:
     ``__call__(x, cutoff)`` (any number of times after one ``set``; ``x`` f64
     [n_total, 3]) returns device tensors ``(center int32 [E], nbr int32 [E],
     vec float32 [E, 3])``: every candidate within the cutoff, rows one after
-    the other, each row in the list's order -- bitwise the host loop's edges."""
+    the other, each row in the list's order -- bitwise the host loop's edges.
+
+    ``set_rank`` / ``check_rank`` / ``rank`` are the same for one rank of a
+    decomposed run (``e3gnn_plist_set_rank`` / ``_check_rank_list`` /
+    ``_rank_build`` + ``_rank_fetch``): ghosts of tags the rank does not own
+    get graph rows in first-seen order, as the parallel pair style gives them."""
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -364,3 +369,70 @@ class ListFilter:
         # the fill pass reads x in stream order: keep it alive until then
         x.record_stream(torch.cuda.current_stream(dev))
         return center, nbr, vec
+
+    @staticmethod
+    def _rank_arrays(row_atom, cand_ptr, cand, atom_class):
+        row_atom = np.ascontiguousarray(row_atom, dtype=np.int32)
+        cand_ptr = np.ascontiguousarray(cand_ptr, dtype=np.int64)
+        cand = np.ascontiguousarray(cand, dtype=np.int32)
+        atom_class = np.ascontiguousarray(atom_class, dtype=np.int32)
+        if cand_ptr.shape != (len(row_atom) + 1,) or (len(cand_ptr) and cand_ptr[-1] != len(cand)):
+            raise ValueError('cand_ptr must have one entry per row plus one and end at len(cand)')
+        return row_atom, cand_ptr, cand, atom_class
+
+    def check_rank(self, row_atom, cand_ptr, cand, atom_class, n_class, neighmask=0x1FFFFFFF):
+        """The check of ``set_rank`` alone, on the host (no device work): raises
+        ``E3GNNError`` naming the atom, row or class that breaks a rule."""
+        import ctypes
+        i32, i64 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+        row_atom, cand_ptr, cand, atom_class = self._rank_arrays(row_atom, cand_ptr, cand, atom_class)
+        self._L.check(self.lib.e3gnn_plist_check_rank_list(
+            len(row_atom), len(atom_class), row_atom.ctypes.data_as(i32),
+            cand_ptr.ctypes.data_as(i64), cand.ctypes.data_as(i32), int(neighmask),
+            atom_class.ctypes.data_as(i32), int(n_class)))
+
+    def set_rank(self, row_atom, cand_ptr, cand, atom_class, n_class, neighmask=0x1FFFFFFF):
+        """Uploads the list of one rank of a decomposed run (the parallel LAMMPS
+        pair style's): as ``set``, with ``atom_class[a]`` in place of
+        ``atom_row`` -- the row in [0, n) of an owned atom and of every ghost
+        carrying an owned atom's tag, ``n + k`` for a ghost whose tag the rank
+        does not own, k in [0, n_class) numbering those tags in any order.  It
+        replaces a list given to ``set``, and the other way round."""
+        import ctypes
+        i32, i64 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+        row_atom, cand_ptr, cand, atom_class = self._rank_arrays(row_atom, cand_ptr, cand, atom_class)
+        s = self._torch.cuda.current_stream(self.device).cuda_stream
+        self.n_total = 0
+        self._L.check(self.lib.e3gnn_plist_set_rank(
+            self._h, len(row_atom), len(atom_class), row_atom.ctypes.data_as(i32),
+            cand_ptr.ctypes.data_as(i64), cand.ctypes.data_as(i32), int(neighmask),
+            atom_class.ctypes.data_as(i32), int(n_class), s))
+        self.n_total = len(atom_class)
+
+    def rank(self, x, cutoff):
+        """After ``set_rank`` (any number of times): the rank graph of the host
+        loop of the parallel pair style, bit for bit.  Returns a dict of device
+        tensors ``center`` / ``nbr`` int32 [E], ``vec`` float32 [E, 3] and
+        ``ghost_atom`` int32 [n_ghost], with ``n_edges`` and ``n_ghost``.  Rows
+        [0, n) are the list rows; a non-owned class with an edge has the row
+        n + r, r counting such classes in the order of their first edge, and
+        ``ghost_atom[r]`` is the atom index of that first edge."""
+        import ctypes
+        torch, dev = self._torch, self.device
+        x = torch.as_tensor(x).to(dev, torch.float64).contiguous()
+        if self.n_total and x.shape != (self.n_total, 3):
+            raise ValueError('x must have one row per atom of the list (owned and ghost)')
+        ne, ng = ctypes.c_int64(), ctypes.c_int64()
+        s = torch.cuda.current_stream(dev).cuda_stream
+        self._L.check(self.lib.e3gnn_plist_rank_build(self._h, x.data_ptr(), float(cutoff),
+                                                      ctypes.byref(ne), ctypes.byref(ng), s))
+        E, G = ne.value, ng.value
+        out = {'center': torch.empty(E, dtype=torch.int32, device=dev),
+               'nbr': torch.empty(E, dtype=torch.int32, device=dev),
+               'vec': torch.empty(E, 3, dtype=torch.float32, device=dev),
+               'ghost_atom': torch.empty(G, dtype=torch.int32, device=dev)}
+        self._L.check(self.lib.e3gnn_plist_rank_fetch(
+            self._h, *[out[k].data_ptr() for k in ('center', 'nbr', 'vec', 'ghost_atom')], s))
+        x.record_stream(torch.cuda.current_stream(dev))
+        out.update(n_edges=E, n_ghost=G)
+        return out
