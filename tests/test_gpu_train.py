@@ -6,6 +6,8 @@ Tolerances (fp32 kernels vs float64): convolution outputs and their first and
 second derivatives 2e-5 relative to the output's max magnitude; model forces
 1e-4 eV/A (north_star), energies 2e-6 relative; parameter gradients of the
 force loss (double backward, create_graph=True) 1e-4 relative in norm.
+The convolution ops run here on one graph of 61 nodes: split 32 only; other
+centre counts in test_gpu_conv_shapes.py.
 """
 import ctypes
 
