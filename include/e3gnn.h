@@ -82,6 +82,23 @@ int e3gnn_abi_version(void);
  * `nequip` self-connection, any radial MLP) on the generic engine; both serve
  * e3gnn_energy_forces and the segment API below.  Returns NULL on failure. */
 e3gnn_model* e3gnn_load(const char* weights_path, const char* manifest_path, int device);
+/* e3gnn_load without files: the manifest as a JSON string and the flat weights
+ * (host, `numel` floats, laid out by the manifest's tensor table) -- both
+ * engines.  Null arguments and a negative numel are E3GNN_ERR_ARG (NULL
+ * returned) before any HIP call. */
+e3gnn_model* e3gnn_load_memory(const char* manifest_json, const float* weights, int64_t numel, int device);
+/* New weights into a loaded fused-family model, in place: the weight-dependent
+ * load steps (embedding, readout, node-linear images, biases, denominators, the
+ * radial MLP's matrices and operand images) re-run on the host over `weights`
+ * (host or device memory, laid out by the manifest the model was loaded with:
+ * a trainable model's flat parameter buffer) and written into the device
+ * buffers the model already owns.  Every buffer keeps its address and size, so
+ * contexts created from the model stay valid.  Drains the device before the
+ * first overwrite (stream-ordered evaluations may still be reading) and
+ * returns with the new weights in place.  E3GNN_ERR_ARG, the model untouched:
+ * null model or weights, numel different from the manifest's total, a
+ * generic-engine model (reload it instead). */
+int e3gnn_set_weights(e3gnn_model* m, const float* weights, int64_t numel, void* stream);
 void e3gnn_free(e3gnn_model* m);
 /* _extra_files metadata: num_species, cutoff, number of interaction layers,
  * comm_size (features exchanged per ghost atom between layers). */
@@ -164,6 +181,42 @@ int e3gnn_loss_efs(int criterion, float delta, int64_t nb, int64_t n, const floa
  * (theta - o) (grad nullable). */
 int e3gnn_ewc_flat(int64_t n, const float* theta, const float* f, const float* o, const float* f_train,
                    float lam, float* grad, float* part, float* value, void* stream);
+
+/* The error recorder's sums of one batch (the reference's ErrorRecorder,
+ * error_recorder.py, without its .item() per metric per batch), accumulated
+ * (+=) into the caller's f64 device buffer sums[E3GNN_ERR_SUMS]: one launch on
+ * `stream`, no synchronisation, no memset, no atomics (fixed-order f64 sums,
+ * bitwise reproducible), capturable in a HIP graph.  Four quantities -- total
+ * energy, energy per atom ((pred - ref) / natoms), force (vectors of 3), stress
+ * (vectors of 6, times s_scale) -- each with E3GNN_ERR_SUMS_PER_QUANTITY sums
+ * at sums[quantity * E3GNN_ERR_SUMS_PER_QUANTITY + sum], d = (f64)pred -
+ * (f64)ref.  A NaN label drops its component alone; a vector enters the vector
+ * sums only when all its components are labelled; the prediction at a dropped
+ * label is never read.  criterion 0: crit(d) = d^2, 1: Huber(delta).
+ * f_pred / f_ref and s_pred / s_ref may both be null (the quantity is
+ * skipped); nb = 0 with n = 0 is a no-op.  Every argument rule is checked
+ * before any HIP call (E3GNN_ERR_ARG). */
+enum {
+  E3GNN_ERRQ_TOTAL_ENERGY = 0,
+  E3GNN_ERRQ_ENERGY = 1, /* per atom */
+  E3GNN_ERRQ_FORCE = 2,
+  E3GNN_ERRQ_STRESS = 3,
+  E3GNN_ERR_QUANTITIES = 4
+};
+enum {
+  E3GNN_ERRS_COMPONENTS = 0, /* labelled components */
+  E3GNN_ERRS_VECTORS = 1,    /* fully labelled vectors */
+  E3GNN_ERRS_ABS = 2,        /* sum |d| over labelled components */
+  E3GNN_ERRS_SQ = 3,         /* sum d^2 over labelled components */
+  E3GNN_ERRS_NORM = 4,       /* sum ||d||_2 over fully labelled vectors */
+  E3GNN_ERRS_CRIT = 5,       /* sum crit(d) over labelled components */
+  E3GNN_ERRS_SQ_VECTORS = 6, /* sum d^2 over the components of fully labelled vectors */
+  E3GNN_ERR_SUMS_PER_QUANTITY = 7
+};
+#define E3GNN_ERR_SUMS (E3GNN_ERR_QUANTITIES * E3GNN_ERR_SUMS_PER_QUANTITY)
+int e3gnn_error_sums(int criterion, float delta, int64_t nb, int64_t n, const float* e_pred,
+                     const float* e_ref, const int64_t* natoms, const float* f_pred, const float* f_ref,
+                     const float* s_pred, const float* s_ref, float s_scale, double* sums, void* stream);
 
 /* Which engine serves the deployment: the channel family of the fused
  * radial-MLP + tensor-product kernels (>= 0: 0 SevenNet-0's 128x0e+64x1e+32x2e,

@@ -36,3 +36,7 @@ EDGE_GRAD = 'edge_grad'
 # loader when edge_index is sorted by centre; the captured fine-tune step then
 # skips its device sort.  It stays on the host when a batch moves.
 EDGE_SORTED = 'edge_index_centre_sorted'
+# config keys of the epoch loop (sevenn/_keys.py): the recorder's rows and the
+# metric that drives the scheduler and the best checkpoint
+ERROR_RECORD = 'error_record'
+BEST_METRIC = 'best_metric'

@@ -23,6 +23,8 @@ SIGNATURES = {
     'e3gnn_last_error': (_cp, []),
     'e3gnn_abi_version': (_c_int, []),
     'e3gnn_load': (_vp, [_cp, _cp, _c_int]),
+    'e3gnn_load_memory': (_vp, [_cp, _vp, _c_i64, _c_int]),
+    'e3gnn_set_weights': (_c_int, [_vp, _vp, _c_i64, _vp]),
     'e3gnn_free': (None, [_vp]),
     'e3gnn_model_info': (_c_int, [_vp, _P(_c_int), _P(_c_f), _P(_c_int), _P(_c_int)]),
     'e3gnn_model_family': (_c_int, [_vp]),
@@ -32,6 +34,7 @@ SIGNATURES = {
     'e3gnn_gemm_reduce': (_c_int, [_c_int, _vp, _vp, _vp]),
     'e3gnn_loss_efs': (_c_int, [_c_int, _c_f, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _c_f, _c_f, _c_f, _c_f, _vp, _vp, _vp, _vp, _vp]),
+    'e3gnn_error_sums': (_c_int, [_c_int, _c_f, _c_i64, _c_i64] + [_vp] * 7 + [_c_f, _vp, _vp]),
     'e3gnn_ewc_flat': (_c_int, [_c_i64, _vp, _vp, _vp, _vp, _c_f, _vp, _vp, _vp, _vp]),
     'e3gnn_ctx_create': (_vp, [_vp]),
     'e3gnn_ctx_free': (None, [_vp]),
@@ -181,6 +184,13 @@ class BatchArrays(ctypes.Structure):
     """e3gnn_batch_arrays (include/e3gnn.h)"""
     _fields_ = [(k, _vp) for k in ('x', 'edge_index', 'edge_vec', 'pbc_shift', 'force_of_atoms',
                                    'batch', 'num_atoms', 'cell_volume', 'total_energy', 'stress')]
+
+
+# e3gnn_error_sums' layout (the enums of include/e3gnn.h)
+ERRQ_TOTAL_ENERGY, ERRQ_ENERGY, ERRQ_FORCE, ERRQ_STRESS, ERR_QUANTITIES = 0, 1, 2, 3, 4
+(ERRS_COMPONENTS, ERRS_VECTORS, ERRS_ABS, ERRS_SQ, ERRS_NORM, ERRS_CRIT, ERRS_SQ_VECTORS,
+ ERR_SUMS_PER_QUANTITY) = range(8)
+ERR_SUMS = ERR_QUANTITIES * ERR_SUMS_PER_QUANTITY
 
 
 class E3GNNError(RuntimeError):

@@ -20,13 +20,15 @@ OBJDIR = os.path.join(HERE, 'csrc', 'build')
 SOURCES = ['api.cpp', 'model_load.cpp', 'api_train.cpp', 'api_nlist.cpp', 'api_plist.cpp', 'api_d3.cpp', 'api_data.cpp',
            'collate.hip', 'generic.cpp',
            'gemm.hip', 'tp.hip', 'node.hip', 'fused.hip', 'neighbor.hip', 'd3.hip', 'train_ops.hip', 'gtp.hip', 'generic.hip', 'mlp_train.hip', 'tgemm.hip',
-           'fcn_train.hip', 'atom_virial.hip', 'segment_sum.hip', 'pairlist.hip', 'scan.hip']
+           'fcn_train.hip', 'atom_virial.hip', 'segment_sum.hip', 'pairlist.hip', 'scan.hip', 'error_sums.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', f'-I{INCLUDE}',
          '-Wall', '-Wno-unused-function']
 # fused.hip: no SLP packing (v_pk_* f32 pairs beside MFMA cost issue slots and
 # double the live registers of the tensor-product loops: 146 -> 123 VGPRs)
-FILE_FLAGS = {'fused.hip': ['-fno-slp-vectorize']}
+# error_sums.hip: products and sums of the f64 terms round separately (the
+# torch definition of the same sums does; error_recorder.py)
+FILE_FLAGS = {'fused.hip': ['-fno-slp-vectorize'], 'error_sums.hip': ['-ffp-contract=off']}
 
 
 def _deps_mtime():

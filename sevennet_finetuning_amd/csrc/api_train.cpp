@@ -16,6 +16,7 @@
 #include "cg_tables.h"
 #include "common.h"
 #include "dbuf.h"
+#include "error_sums.h"
 #include "fcn_act.h"
 #include "fcn_train.h"
 #include "gtp.h"
@@ -167,6 +168,26 @@ int e3gnn_ewc_flat(int64_t n, const float* theta, const float* f, const float* o
   HIPCHK(launch_ewc_flat(n, theta, f, o, f_train, lam, grad, part, s));
   // fixed-order block sums into part[n ...], then their sum (node.hip launch_sum)
   HIPCHK(launch_sum(n, part, part + n, value, s));
+  return E3GNN_OK;
+}
+
+int e3gnn_error_sums(int criterion, float delta, int64_t nb, int64_t n, const float* e_pred,
+                     const float* e_ref, const int64_t* natoms, const float* f_pred, const float* f_ref,
+                     const float* s_pred, const float* s_ref, float s_scale, double* sums, void* stream) {
+  // (every rule before any HIP call)
+  if (!sums) return fail(E3GNN_ERR_ARG, "e3gnn_error_sums: null sums buffer");
+  if (criterion != 0 && criterion != 1)
+    return fail(E3GNN_ERR_ARG, "e3gnn_error_sums: criterion must be 0 (mse) or 1 (huber)");
+  if (nb < 0 || n < 0 || nb >= (int64_t)1 << 31 || n >= (int64_t)1 << 31)
+    return fail(E3GNN_ERR_ARG, "e3gnn_error_sums: nb / n out of range [0, 2^31)");
+  if ((e_pred == nullptr) != (e_ref == nullptr) || (f_pred == nullptr) != (f_ref == nullptr) ||
+      (s_pred == nullptr) != (s_ref == nullptr))
+    return fail(E3GNN_ERR_ARG, "e3gnn_error_sums: a prediction and its reference go together");
+  if (nb > 0 && !natoms) return fail(E3GNN_ERR_ARG, "e3gnn_error_sums: null natoms with nb > 0");
+  if (nb > 0 && !e_pred) return fail(E3GNN_ERR_ARG, "e3gnn_error_sums: null energies with nb > 0");
+  if (nb == 0 && n == 0) return E3GNN_OK;
+  ErrSumArgs a{criterion, delta, nb, n, e_pred, e_ref, natoms, f_pred, f_ref, s_pred, s_ref, s_scale, sums};
+  HIPCHK(launch_error_sums(a, (hipStream_t)stream));
   return E3GNN_OK;
 }
 

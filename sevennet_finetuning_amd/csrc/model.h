@@ -94,6 +94,10 @@ struct e3gnn_model {
     DBuf w1b;            // layer 1's operand, w2b order (fused.h)
   };
   std::vector<Mlp> mlp;
+  // the manifest the fused-family model was loaded with and the extent of its
+  // tensor table: e3gnn_set_weights lays a new flat array out by them
+  std::string manifest_json;
+  int64_t flat_numel = 0;
   // any other nequip-family deployment: the generic engine (generic.cpp)
   e3gnn::GenModel* gen = nullptr;
   ~e3gnn_model() {

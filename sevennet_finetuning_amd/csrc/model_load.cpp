@@ -67,6 +67,7 @@ int build_linear(Linear& L, const Irreps& in, const Irreps& out, const float* w,
   std::vector<float> W, WT;
   int in_off = 0;
   size_t woff = 0;
+  L.blocks.clear();   // (a refresh rebuilds the same table)
   L.din = irreps_dim(in);
   L.dout = irreps_dim(out);
   for (auto& a : in) {
@@ -102,6 +103,8 @@ int build_linear(Linear& L, const Irreps& in, const Irreps& out, const float* w,
 int build_pair(LinPair& P, const Linear& a, bool ta, const Linear* b, bool tb) {
   std::vector<float> W;
   size_t matched = 0;
+  P.blocks.clear();   // (a refresh rebuilds the same table)
+  P.ok = false;
   for (auto& k : a.blocks) {
     PairBlock pb;
     pb.l = k.l;
@@ -274,12 +277,20 @@ int fused_family(const minijson::Value& man) {
 }
 
 // ------------------------------------------------------------ the steps of e3gnn_load
-// The deployment as read from disk: the manifest, the flat weights and the
-// manifest's tensor index, with checked access by name.
+// The deployment as read from disk or taken from memory: the manifest (and
+// its text), the flat weights and the manifest's tensor index, with checked
+// access by name.  The steps come in two kinds: those that read the manifest
+// alone (load_header, load_block_irreps: run once, they size the model) and
+// those that read the weights (load_weights and below: each writes slot t of
+// the model's tables and uploads into the buffers already there, so
+// e3gnn_set_weights re-runs them over a new flat array and every device
+// buffer keeps its address and size).
 struct Deploy {
+  std::string text;
   minijson::Value man;
   std::vector<float> flat;
   std::map<std::string, std::pair<size_t, size_t>> T;   // name -> (offset, numel)
+  size_t total = 0;                                      // the tensor table's extent
   bool has_bias = false;                                 // use_bias_in_linear
 
   const float* get(const std::string& n, size_t expect = 0) const {
@@ -310,8 +321,9 @@ int read_deploy(Deploy& D, const char* weights_path, const char* manifest_path) 
     if (!f) return fail(E3GNN_ERR_IO, std::string("cannot open manifest ") + manifest_path);
     std::stringstream ss;
     ss << f.rdbuf();
+    D.text = ss.str();
     std::string err;
-    if (!minijson::parse(ss.str(), D.man, err)) return fail(E3GNN_ERR_IO, "manifest parse error: " + err);
+    if (!minijson::parse(D.text, D.man, err)) return fail(E3GNN_ERR_IO, "manifest parse error: " + err);
   }
   std::ifstream f(weights_path, std::ios::binary | std::ios::ate);
   if (!f) return fail(E3GNN_ERR_IO, std::string("cannot open weights ") + weights_path);
@@ -322,8 +334,18 @@ int read_deploy(Deploy& D, const char* weights_path, const char* manifest_path) 
   return E3GNN_OK;
 }
 
-// the manifest's scalars and irreps, and the tensor index of D
-void load_header(e3gnn_model* m, Deploy& D, int family) {
+// the tensor index of D's manifest
+void index_tensors(Deploy& D) {
+  for (auto& t : D.man["tensors"].arr()) {
+    const size_t off = (size_t)t["offset"].num(), n = (size_t)t["numel"].num();
+    D.T[t["name"].str()] = {off, n};
+    D.total = std::max(D.total, off + n);
+  }
+  D.has_bias = D.man.has("use_bias_in_linear") && D.man["use_bias_in_linear"].boolean();
+}
+
+// the manifest's scalars and irreps; the per-block tables sized for their slots
+void load_header(e3gnn_model* m, const Deploy& D, int family) {
   const minijson::Value& man = D.man;
   // the knobs this engine does not read must hold SevenNet-0's values (the
   // same predicate as nn.sevennet0_kinds)
@@ -348,9 +370,14 @@ void load_header(e3gnn_model* m, Deploy& D, int family) {
     throw std::runtime_error("silu_norm mismatch");
   for (auto& s : man["irreps_manual"].arr()) m->irreps.push_back(merged(parse_irreps(s.str())));
   if ((int)m->irreps.size() != m->nlayer + 1) throw std::runtime_error("irreps_manual length");
-  for (auto& t : man["tensors"].arr())
-    D.T[t["name"].str()] = {(size_t)t["offset"].num(), (size_t)t["numel"].num()};
-  D.has_bias = man.has("use_bias_in_linear") && man["use_bias_in_linear"].boolean();
+  const size_t L = (size_t)m->nlayer;
+  m->denom.assign(L, 0.f);
+  m->W.assign(L, 0);
+  m->mlp.resize(L);
+  m->b_si1.resize(L);
+  m->b_si2.resize(L);
+  for (auto* v : {&m->sc, &m->si1, &m->si2}) v->resize(L);
+  for (auto* v : {&m->nl_si1, &m->nl_si1t, &m->nl_si2t, &m->nl_fwd, &m->nl_bwd}) v->resize(L);
 }
 
 // radial basis coefficients and the species embedding
@@ -438,9 +465,9 @@ void load_readout(e3gnn_model* m, const Deploy& D) {
   must_upload(m->shift, shift);
 }
 
-// block t's irreps: the gate's input row, the gate layout, the convolution's
-// mid irreps and denominator; the kernel tables of its kind code must match
-void load_block_irreps(e3gnn_model* m, const Deploy& D, int t) {
+// block t's irreps: the gate's input row, the gate layout and the
+// convolution's mid irreps; the kernel tables of its kind code must match
+void load_block_irreps(e3gnn_model* m, int t) {
   const Irreps& xin = m->irreps[t];
   const Irreps& xout = m->irreps[t + 1];
   const bool last = t == m->nlayer - 1;
@@ -477,45 +504,41 @@ void load_block_irreps(e3gnn_model* m, const Deploy& D, int t) {
   }
   m->gin.push_back(gin);
   m->mid.push_back(mid);
-  m->denom.push_back(*D.get(std::to_string(t) + "_convolution.denominator", 1));
 }
 
-// block t's node linears, their biases and the k_nodelin problem sets
+// block t's denominator, node linears, their biases and the k_nodelin problem sets
 void load_block_linears(e3gnn_model* m, const Deploy& D, int t) {
   const Irreps &xin = m->irreps[t], &gin = m->gin[t], &mid = m->mid[t];
   const std::string p = std::to_string(t);
-  const float den = m->denom[t];
-  auto mk = [&](const std::string& name, const Irreps& a, const Irreps& b, double extra) {
-    auto L = std::make_unique<Linear>();
+  const float den = m->denom[t] = *D.get(p + "_convolution.denominator", 1);
+  auto mk = [&](std::unique_ptr<Linear>& L, const std::string& name, const Irreps& a, const Irreps& b,
+                double extra) {
+    if (!L) L = std::make_unique<Linear>();
     if (build_linear(*L, a, b, D.get(name), D.numel(name), extra) != 0)
       throw std::runtime_error("linear " + name);
-    return L;
   };
   trace_point("load:layer-begin");
-  m->sc.push_back(mk(p + "_self_connection_intro.linear.weight", xin, gin, 1.0));
+  mk(m->sc[t], p + "_self_connection_intro.linear.weight", xin, gin, 1.0);
   trace_point("load:sc");
-  m->si1.push_back(mk(p + "_self_interaction_1.linear.weight", xin, xin, 1.0));
+  mk(m->si1[t], p + "_self_interaction_1.linear.weight", xin, xin, 1.0);
   // backward of si2 feeds dE/dagg_raw = dE/dagg / denominator (convolution.py:117-118)
-  m->si2.push_back(mk(p + "_self_interaction_2.linear.weight", mid, gin, 1.0 / den));
+  mk(m->si2[t], p + "_self_interaction_2.linear.weight", mid, gin, 1.0 / den);
   // their biases (the self-connection has none, model_build.py:281-282):
   // si2's covers the scalars and the gate pre-activations, and is not
   // divided by the denominator (only si2's weights carry it)
-  m->b_si1.emplace_back();
-  m->b_si2.emplace_back();
   if (D.has_bias) {
     must_upload(m->b_si1[t], D.bias(p + "_self_interaction_1.linear.bias", xin));
     must_upload(m->b_si2[t], D.bias(p + "_self_interaction_2.linear.bias", gin));
   }
-  auto pair = [&](const Linear& a, bool ta, const Linear* b, bool tb) {
-    auto P = std::make_unique<LinPair>();
+  auto pair = [&](std::unique_ptr<LinPair>& P, const Linear& a, bool ta, const Linear* b, bool tb) {
+    if (!P) P = std::make_unique<LinPair>();
     if (build_pair(*P, a, ta, b, tb) < 0) throw std::runtime_error("upload");
-    return P;
   };
-  m->nl_si1.push_back(pair(*m->si1[t], false, nullptr, false));
-  m->nl_si1t.push_back(pair(*m->si1[t], true, nullptr, false));
-  m->nl_si2t.push_back(pair(*m->si2[t], true, nullptr, false));
-  m->nl_fwd.push_back(pair(*m->si2[t], false, m->sc[t].get(), false));
-  m->nl_bwd.push_back(pair(*m->si1[t], true, m->sc[t].get(), true));
+  pair(m->nl_si1[t], *m->si1[t], false, nullptr, false);
+  pair(m->nl_si1t[t], *m->si1[t], true, nullptr, false);
+  pair(m->nl_si2t[t], *m->si2[t], true, nullptr, false);
+  pair(m->nl_fwd[t], *m->si2[t], false, m->sc[t].get(), false);
+  pair(m->nl_bwd[t], *m->si1[t], true, m->sc[t].get(), true);
 }
 
 // a[r][c] * s, optionally transposed
@@ -542,9 +565,8 @@ void load_block_mlp(e3gnn_model* m, const Deploy& D, int t) {
   int kdx = 0, Wexp = 0, kdm = 0;
   fused_kind_dims(m->kcode(t), &kdx, &Wexp, &kdm);
   if (W != Wexp || W % 16) throw std::runtime_error("radial weight width mismatch");
-  m->W.push_back(W);
-  m->mlp.emplace_back();
-  auto& mm = m->mlp.back();
+  m->W[t] = W;
+  auto& mm = m->mlp[t];
   const double s0 = 1.0 / std::sqrt(8.0), s1 = 1.0 / 8.0, s2 = 1.0 / 8.0;
   const auto a0 = scaled(w0, 8, 64, s0, false), a1 = scaled(w1, 64, 64, s1, false),
              a2 = scaled(w2, 64, W, s2, false);
@@ -584,11 +606,20 @@ void load_block_mlp(e3gnn_model* m, const Deploy& D, int t) {
   trace_point("load:mlp");
 }
 
-}  // namespace
+// every weight-dependent step, over the tables load_header / load_block_irreps sized
+void load_weights(e3gnn_model* m, const Deploy& D) {
+  load_embedding(m, D);
+  load_readout(m, D);
+  for (int t = 0; t < m->nlayer; ++t) {
+    load_block_linears(m, D, t);
+    load_block_mlp(m, D, t);
+  }
+}
 
-extern "C" {
-
-e3gnn_model* e3gnn_load(const char* weights_path, const char* manifest_path, int device) {
+// e3gnn_load / e3gnn_load_memory: `read` fills D's manifest and weights
+// (nonzero with the error set when it cannot)
+template <class Read>
+e3gnn_model* load_model(int device, Read read) {
   auto m = std::make_unique<e3gnn_model>();
   m->device = device;
   trace_point("load:entry");
@@ -598,7 +629,7 @@ e3gnn_model* e3gnn_load(const char* weights_path, const char* manifest_path, int
   }
   trace_point("load:hipSetDevice");
   Deploy D;
-  if (read_deploy(D, weights_path, manifest_path)) return nullptr;
+  if (read(D)) return nullptr;
   try {
     if (D.man["model_type"].str() != "E3_equivariant_model")
       throw std::runtime_error("unsupported model_type");
@@ -614,14 +645,12 @@ e3gnn_model* e3gnn_load(const char* weights_path, const char* manifest_path, int
       (void)hipGetLastError();
       return m.release();
     }
+    index_tensors(D);
     load_header(m.get(), D, family);
-    load_embedding(m.get(), D);
-    load_readout(m.get(), D);
-    for (int t = 0; t < m->nlayer; ++t) {
-      load_block_irreps(m.get(), D, t);
-      load_block_linears(m.get(), D, t);
-      load_block_mlp(m.get(), D, t);
-    }
+    for (int t = 0; t < m->nlayer; ++t) load_block_irreps(m.get(), t);
+    load_weights(m.get(), D);
+    m->manifest_json = std::move(D.text);
+    m->flat_numel = (int64_t)D.total;
   } catch (const std::exception& ex) {
     fail(E3GNN_ERR_IO, std::string("model load: ") + ex.what());
     return nullptr;
@@ -631,6 +660,70 @@ e3gnn_model* e3gnn_load(const char* weights_path, const char* manifest_path, int
   // thread-local HIP error state dirty (torch re-reads it after its own calls)
   (void)hipGetLastError();
   return m.release();
+}
+
+}  // namespace
+
+extern "C" {
+
+e3gnn_model* e3gnn_load(const char* weights_path, const char* manifest_path, int device) {
+  return load_model(device, [&](Deploy& D) { return read_deploy(D, weights_path, manifest_path); });
+}
+
+e3gnn_model* e3gnn_load_memory(const char* manifest_json, const float* weights, int64_t numel, int device) {
+  if (!manifest_json || !weights || numel < 0) {
+    fail(E3GNN_ERR_ARG, "e3gnn_load_memory: null manifest or weights, or a negative numel");
+    return nullptr;
+  }
+  return load_model(device, [&](Deploy& D) {
+    D.text = manifest_json;
+    std::string err;
+    if (!minijson::parse(D.text, D.man, err)) return fail(E3GNN_ERR_IO, "manifest parse error: " + err);
+    D.flat.assign(weights, weights + numel);
+    return (int)E3GNN_OK;
+  });
+}
+
+int e3gnn_set_weights(e3gnn_model* m, const float* weights, int64_t numel, void* stream) {
+  if (!m) return fail(E3GNN_ERR_ARG, "e3gnn_set_weights: null model");
+  if (!weights) return fail(E3GNN_ERR_ARG, "e3gnn_set_weights: null weights");
+  if (m->gen)
+    return fail(E3GNN_ERR_ARG, "e3gnn_set_weights: a generic-engine model has no in-place refresh "
+                               "(load it again with e3gnn_load_memory)");
+  if (numel != m->flat_numel)
+    return fail(E3GNN_ERR_ARG, "e3gnn_set_weights: numel " + std::to_string(numel) + ", the manifest's tensors hold " +
+                                   std::to_string(m->flat_numel));
+  HIPCHK(hipSetDevice(m->device));
+  // Stream-ordered evaluations may still read the buffers about to be
+  // overwritten, and `weights` may be written by work queued on `stream`: drain
+  // the device (the hazard DBuf::ensure documents), then take the weights
+  HIPCHK(hipDeviceSynchronize());
+  Deploy D;
+  D.flat.resize((size_t)numel);
+  {
+    hipPointerAttribute_t at{};
+    const bool dev = hipPointerGetAttributes(&at, weights) == hipSuccess &&
+                     (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged);
+    (void)hipGetLastError();   // (a plain host pointer is "invalid value" to some runtimes)
+    if (dev) {
+      HIPCHK(hipMemcpyAsync(D.flat.data(), weights, (size_t)numel * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+      HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    } else {
+      std::copy(weights, weights + numel, D.flat.begin());
+    }
+  }
+  try {
+    std::string err;
+    if (!minijson::parse(m->manifest_json, D.man, err)) throw std::runtime_error("manifest: " + err);
+    index_tensors(D);
+    // the manifest passed every shape check at load and the packers read
+    // nothing else: only a HIP failure can stop the steps below
+    load_weights(m, D);
+  } catch (const std::exception& ex) {
+    return fail(E3GNN_ERR_HIP, std::string("e3gnn_set_weights: ") + ex.what());
+  }
+  (void)hipGetLastError();
+  return E3GNN_OK;
 }
 
 void e3gnn_free(e3gnn_model* m) { delete m; }

@@ -69,23 +69,35 @@ def segment_sum(rows, ptr):
 
 
 class E3GNNModel:
-    """A loaded deployment (weights.bin + manifest.json) on one HIP device."""
+    """A loaded deployment on one HIP device: weights.bin + manifest.json of
+    ``model_dir``, or, without files, a ``manifest`` dict and the flat
+    ``weights`` it lays out (e3gnn_load_memory; ``from_trainable``)."""
 
-    def __init__(self, model_dir=os.path.join(ASSETS, 'sevennet0'), device=None):
+    def __init__(self, model_dir=os.path.join(ASSETS, 'sevennet0'), device=None, manifest=None,
+                 weights=None):
         self.lib = _lib.load()
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device())
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise _lib.E3GNNError(f'the HIP path needs a GPU device, got {self.device}')
-        self.model_dir = model_dir
-        with open(os.path.join(model_dir, 'manifest.json')) as f:
-            self.manifest = json.load(f)
+        if (manifest is None) != (weights is None):
+            raise ValueError('manifest and weights go together')
+        idx = self.device.index if self.device.index is not None else 0
+        if manifest is not None:
+            self.model_dir = None
+            self.manifest = json.loads(json.dumps(manifest))
+            w = self._host_weights(weights)
+            h = self.lib.e3gnn_load_memory(json.dumps(self.manifest).encode(), w.ctypes.data,
+                                           int(w.size), idx)
+        else:
+            self.model_dir = model_dir
+            with open(os.path.join(model_dir, 'manifest.json')) as f:
+                self.manifest = json.load(f)
+            h = self.lib.e3gnn_load(os.path.join(model_dir, 'weights.bin').encode(),
+                                    os.path.join(model_dir, 'manifest.json').encode(), idx)
         self.chemical_symbols = list(self.manifest['chemical_symbols'])
         self.cutoff = float(self.manifest['cutoff'])
-        idx = self.device.index if self.device.index is not None else 0
-        h = self.lib.e3gnn_load(os.path.join(model_dir, 'weights.bin').encode(),
-                                os.path.join(model_dir, 'manifest.json').encode(), idx)
         if not h:
             raise _lib.E3GNNError(self.lib.e3gnn_last_error().decode())
         self._model = h
@@ -103,6 +115,35 @@ class E3GNNModel:
         # evaluation is enqueued (stream order, like a torch module) rather than
         # synchronising; E3GNN_SYNC=1 restores the blocking call
         self.set_stream_ordered(os.environ.get('E3GNN_SYNC', '0') != '1')
+
+    @staticmethod
+    def _host_weights(weights):
+        import numpy as np
+        if torch.is_tensor(weights):
+            weights = weights.detach().to('cpu', torch.float32).numpy()
+        return np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+
+    @classmethod
+    def from_trainable(cls, model, device=None):
+        """The served engine of a trainable model's current parameters
+        (``SevenNetTrainable.manifest`` / ``.flat``), without deployment files."""
+        return cls(device=device or model.flat.device, manifest=model.manifest, weights=model.flat)
+
+    def set_weights(self, weights):
+        """New weights in place (e3gnn_set_weights): a flat tensor or array laid
+        out by the manifest the model was loaded with (``SevenNetTrainable.flat``).
+        A float32 device tensor is read where it is; the repack runs on the
+        host through the load's own packers.  The device buffers keep their
+        addresses: contexts and anything holding them stay valid.  Drains the
+        device; returns with the new weights in place."""
+        if torch.is_tensor(weights) and weights.is_cuda and weights.dtype == torch.float32:
+            w = weights.detach().contiguous().view(-1)
+            with torch.cuda.device(w.device):
+                _lib.check(self.lib.e3gnn_set_weights(self._model, w.data_ptr(), int(w.numel()),
+                                                      torch.cuda.current_stream(w.device).cuda_stream))
+            return
+        w = self._host_weights(weights)
+        _lib.check(self.lib.e3gnn_set_weights(self._model, w.ctypes.data, int(w.size), None))
 
     # --------------------------------------------------------------- metadata
     def type_map(self):

@@ -549,6 +549,7 @@ class Trainer:
             if self.hip_graph else None
         # (None: the loss by autograd over its torch expression)
         self._fused_loss = self._fused_loss_plan() if self.explicit is not None else None
+        self._served = None   # validate()'s E3GNNModel of this model, made on first use
 
     # ---- the pieces of one step
     def zero_grad(self):
@@ -674,26 +675,51 @@ class Trainer:
         dist.all_reduce(g)
         g.div_(self.world)
 
-    def train_step(self, batch):
+    def _record(self, recorder, output, batch, fresh=False):
+        """One forward's (output, batch) into ``recorder`` (error_recorder.py):
+        one launch on the current stream, no synchronisation.  ``fresh``: the
+        call follows this forward's loss_backward, whose EWC term is still in
+        place; otherwise a recorder with an EWCLoss row has it computed."""
+        if recorder is None:
+            return
+        ewc = None
+        if recorder.wants_ewc:
+            for f, w in self.loss_functions:
+                if not isinstance(f, EWCLoss):
+                    continue
+                if fresh and self._fused_loss is not None and self._fused_loss['ewc'] is not None:
+                    ewc = self._fused_loss['ewc_val'] * w
+                else:
+                    with torch.no_grad():
+                        ewc = f.get_loss(output, self.model) * w
+        recorder.update(output, batch, ewc=ewc)
+
+    def train_step(self, batch, error_recorder=None):
         """One optimizer step of Trainer.run_one_epoch (trainer.py:55-68)."""
         self.zero_grad()
         loss, output = self.loss_backward(batch)
+        self._record(error_recorder, output, batch, fresh=True)
         self.optimizer.step()
         return loss.detach(), output
 
-    def rehearsal_step(self, batch, batch_mem):
+    def rehearsal_step(self, batch, batch_mem, error_recorder=None, mem_recorder=None):
         """One iteration of RehearsalTrainer.run_one_epoch_rehearsal
         (trainer.py:174-206): zero_grad once, backward+step on the new batch,
-        then backward (accumulating) + step on the memory batch."""
+        then backward (accumulating) + step on the memory batch; each forward
+        recorded right after its backward (``error_recorder`` the new batch,
+        ``mem_recorder`` the memory batch)."""
+        recorders = (error_recorder, mem_recorder)
         if self._graphed is not None:
-            return self._graphed(batch, batch_mem)
-        return self._rehearsal_body(batch, batch_mem)
+            return self._graphed(batch, batch_mem, recorders)
+        return self._rehearsal_body(batch, batch_mem, recorders=recorders)
 
-    def _rehearsal_body(self, batch, batch_mem, graphs=(None, None)):
+    def _rehearsal_body(self, batch, batch_mem, graphs=(None, None), recorders=(None, None)):
         self.zero_grad()
-        loss, _ = self.loss_backward(batch, graphs[0])
+        loss, out = self.loss_backward(batch, graphs[0])
+        self._record(recorders[0], out, batch, fresh=True)
         self.optimizer.step()
-        mem_loss, _ = self.loss_backward(batch_mem, graphs[1])
+        mem_loss, out = self.loss_backward(batch_mem, graphs[1])
+        self._record(recorders[1], out, batch_mem, fresh=True)
         self.optimizer.step()
         return loss.detach(), mem_loss.detach()
 
@@ -709,18 +735,69 @@ class Trainer:
             mark_edges_sorted(out)
         return out
 
-    def run_one_epoch(self, loader, is_train=False):
+    def run_one_epoch(self, loader, is_train=False, error_recorder=None):
         self.model.train(is_train)
         losses = []
         for batch in loader:
             batch = self._to_device(batch, non_blocking=True)
             if is_train:
-                losses.append(self.train_step(batch)[0])
+                losses.append(self.train_step(batch, error_recorder)[0])
             else:
-                losses.append(self.total_loss(self.model(batch)).detach())
+                output = self.model(batch)
+                losses.append(self.total_loss(output).detach())
+                self._record(error_recorder, output, batch)
+        if error_recorder is not None and self.distributed:
+            error_recorder.reduce()
         return losses
 
-    def run_one_epoch_rehearsal(self, loader, memloader, is_train=False):
+    def _served_output(self, batch, want_stress):
+        """The served engine's predictions of one (padded or plain) batch as
+        the trainable's output keys.  No padded edge touches a real atom and
+        the recorder never reads a dummy slot's prediction, so DeviceLoader
+        batches go in as they are; ``atom_ptr`` is a device prefix sum."""
+        batch = GraphedRehearsalStep._centre_sorted(batch)
+        ei = batch[KEY.EDGE_IDX]
+        na = batch[KEY.NUM_ATOMS].view(-1)
+        atom_ptr = torch.zeros(na.numel() + 1, dtype=torch.int32, device=self.device)
+        atom_ptr[1:] = torch.cumsum(na, 0)
+        res = self._served.energy_forces_batch(batch[KEY.NODE_FEATURE], ei[0], ei[1],
+                                               batch[KEY.EDGE_VEC], atom_ptr, want_virial=want_stress)
+        out = {KEY.PRED_TOTAL_ENERGY: res['energy'], KEY.PRED_FORCE: res['forces'],
+               KEY.ATOMIC_ENERGY: res['atomic_energy'].unsqueeze(-1)}
+        if want_stress:
+            # virial6 = -dE/dstrain = inferred_stress * volume, the same order
+            # (xx, yy, zz, xy, yz, zx) and sign as the trainable's inferred_stress
+            vol = batch[KEY.CELL_VOLUME].to(self.device, torch.float32).view(-1, 1)
+            out[KEY.PRED_STRESS] = res['virial'] / vol
+        return out
+
+    def validate(self, loader, error_recorder):
+        """The validation pass on the served kernels: the trainer's own
+        ``E3GNNModel`` of this model (``from_trainable`` on first use) takes the
+        current parameters in place (``set_weights``, once per call), evaluates
+        every batch by ``energy_forces_batch`` and records it.  For a model the
+        explicit step supports, on a GPU in float32; any other model takes
+        ``run_one_epoch(loader, False, error_recorder)``.  Returns the recorder."""
+        from . import train_explicit
+        m = self.model
+        served = (self.device.type == 'cuda' and getattr(m, 'dtype', None) == torch.float32
+                  and hasattr(m, 'blocks') and train_explicit.supported(m))
+        if served and self._served is None:
+            from .model import E3GNNModel
+            self._served = E3GNNModel.from_trainable(m)
+        if not served or self._served.family < 0:
+            self.run_one_epoch(loader, False, error_recorder)
+            return error_recorder
+        self._served.set_weights(m.flat)
+        for batch in loader:
+            batch = self._to_device(batch, non_blocking=True)
+            self._record(error_recorder, self._served_output(batch, error_recorder.stress), batch)
+        if self.distributed:
+            error_recorder.reduce()
+        return error_recorder
+
+    def run_one_epoch_rehearsal(self, loader, memloader, is_train=False, error_recorder=None,
+                                mem_recorder=None):
         self.model.train(is_train)
         mem_iter = iter(memloader)
         out = []
@@ -733,10 +810,19 @@ class Trainer:
             batch = self._to_device(batch)
             batch_mem = self._to_device(batch_mem)
             if is_train:
-                out.append(self.rehearsal_step(batch, batch_mem))
+                if error_recorder is None and mem_recorder is None:
+                    out.append(self.rehearsal_step(batch, batch_mem))
+                else:
+                    out.append(self.rehearsal_step(batch, batch_mem, error_recorder, mem_recorder))
             else:
-                out.append((self.total_loss(self.model(batch)).detach(),
-                            self.total_loss(self.model(batch_mem)).detach()))
+                o, om = self.model(batch), self.model(batch_mem)
+                out.append((self.total_loss(o).detach(), self.total_loss(om).detach()))
+                self._record(error_recorder, o, batch)
+                self._record(mem_recorder, om, batch_mem)
+        if self.distributed:
+            for rec in (error_recorder, mem_recorder):
+                if rec is not None:
+                    rec.reduce()
         return out
 
     def scheduler_step(self, metric=None):
@@ -825,7 +911,7 @@ class GraphedRehearsalStep:
                 if torch.is_tensor(s.get(k)):
                     s[k].copy_(v)
 
-    def _capture(self, batch, mem):
+    def _capture(self, batch, mem, recorders=(None, None)):
         tr = self.tr
         sb = {k: v.clone() for k, v in batch.items()}
         sm = {k: v.clone() for k, v in mem.items()}
@@ -839,10 +925,13 @@ class GraphedRehearsalStep:
         dist_flag, tr.distributed = tr.distributed, False
         try:
             with torch.cuda.stream(side):
+                # the warm-ups record like the captured step (the same launches)
+                # and are rolled back out of the sums like out of the parameters
+                rec_snaps = [r.snapshot() if r is not None else None for r in recorders]
                 first = not tr.optimizer.state
                 if first:   # create the optimizer state, then undo the update
                     snap0 = tr.model.flat.detach().clone()
-                    tr._rehearsal_body(sb, sm, graphs)
+                    tr._rehearsal_body(sb, sm, graphs, recorders)
                     with torch.no_grad():
                         tr.model.flat.copy_(snap0)
                     for s in tr.optimizer.state.values():
@@ -851,24 +940,29 @@ class GraphedRehearsalStep:
                                 v.zero_()
                 snap = self._state()
                 for _ in range(2):
-                    tr._rehearsal_body(sb, sm, graphs)
+                    tr._rehearsal_body(sb, sm, graphs, recorders)
                 self._restore(snap)
+                for r, rs in zip(recorders, rec_snaps):
+                    if r is not None:
+                        r.restore(rs)
         finally:
             tr.distributed = dist_flag
         torch.cuda.current_stream().wait_stream(side)
         if not tr.distributed:
             g = torch.cuda.CUDAGraph()
             with _capturing(g):
-                loss, mloss = tr._rehearsal_body(sb, sm, graphs)
+                loss, mloss = tr._rehearsal_body(sb, sm, graphs, recorders)
             return {'g': [g], 'b': sb, 'm': sm, 'graphs': graphs, 'out': (loss, mloss)}
         segs = [torch.cuda.CUDAGraph() for _ in range(3)]
         with _capturing(segs[0]):
             tr.zero_grad()
-            loss, _ = tr.loss_backward(sb, graphs[0], reduce=False)
+            loss, out = tr.loss_backward(sb, graphs[0], reduce=False)
+            tr._record(recorders[0], out, sb, fresh=True)
         pool = segs[0].pool()
         with _capturing(segs[1], pool=pool):
             tr.optimizer.step()
-            mloss, _ = tr.loss_backward(sm, graphs[1], reduce=False)
+            mloss, out = tr.loss_backward(sm, graphs[1], reduce=False)
+            tr._record(recorders[1], out, sm, fresh=True)
         with _capturing(segs[2], pool=pool):
             tr.optimizer.step()
         return {'g': segs, 'b': sb, 'm': sm, 'graphs': graphs,
@@ -891,17 +985,25 @@ class GraphedRehearsalStep:
                 out[k] = b[k][perm]
         return out
 
-    def __call__(self, batch, mem):
+    def __call__(self, batch, mem, recorders=(None, None)):
         given = (batch, mem)
         batch, mem = self._centre_sorted(batch), self._centre_sorted(mem)
         self.stats['device_sorts'] += (batch is not given[0]) + (mem is not given[1])
-        key = (self._sig(batch), self._sig(mem))
+        # a captured graph records into the sums buffers it was captured with:
+        # their identity is part of the key, so attaching, detaching or
+        # swapping recorders captures anew instead of replaying a graph that
+        # writes elsewhere or nowhere
+        rec_key = tuple(r.buffer(self.tr.device).data_ptr() if r is not None else None
+                        for r in recorders)
+        key = (self._sig(batch), self._sig(mem)) if rec_key == (None, None) else \
+            (self._sig(batch), self._sig(mem), rec_key)
         ent = self.cache.get(key)
         if ent is None:
             if len(self.cache) >= self.max_graphs:
                 self.stats['eager'] += 1
-                return self.tr._rehearsal_body(batch, mem)
-            ent = self.cache[key] = self._capture(batch, mem)
+                return self.tr._rehearsal_body(batch, mem, recorders=recorders)
+            ent = self.cache[key] = self._capture(batch, mem, recorders)
+            ent['recorders'] = recorders   # (their buffers stay alive with the graph)
             self.stats['captured'] += 1
         else:
             self.stats['replayed'] += 1
@@ -953,3 +1055,41 @@ def setup_distributed(backend=None):
         kw = {'device_id': device} if (gpu and backend == 'nccl') else {}
         dist.init_process_group(backend, **kw)
     return dist.get_rank(), dist.get_world_size(), local, device
+
+
+# ------------------------------------------------------------------ epoch loop
+def csv_header(recorder):
+    """The reference's log.csv header of a recorder's metrics
+    (processing_epoch_with_rehearsal.py:29-35)."""
+    from .error_recorder import csv_header as header
+    return header(recorder)
+
+
+def rehearsal_epochs(trainer, train_loader, mem_loader, valid_loader, config, epochs, start_epoch=0):
+    """The epoch loop of processing_epoch_with_rehearsal.py:47-97 without its
+    files (checkpoints and logs stay with the caller): per epoch a rehearsal
+    pass over (train_loader, mem_loader) with the train and memory recorders,
+    ``validate`` on valid_loader, ``scheduler_step(val)`` with ``val`` the first
+    validation metric whose key contains ``config['best_metric']``.  Yields
+    one row dict per epoch: ``Epoch``, ``Learning_rate`` (the epoch's), then
+    ``Train_k``, ``Valid_k``, ``Memory_k`` per metric key k (``csv_header``)."""
+    from .error_recorder import ErrorRecorder
+    train_rec, valid_rec, mem_rec = (ErrorRecorder.from_config(config) for _ in range(3))
+    best_metric = config[KEY.BEST_METRIC]
+    for epoch in range(start_epoch, start_epoch + epochs):
+        lr = float(trainer.get_lr())
+        trainer.run_one_epoch_rehearsal(train_loader, mem_loader, is_train=True,
+                                        error_recorder=train_rec, mem_recorder=mem_rec)
+        train_err, memory_err = train_rec.epoch_forward(), mem_rec.epoch_forward()
+        trainer.validate(valid_loader, valid_rec)
+        valid_err = valid_rec.epoch_forward()
+        row = {'Epoch': epoch, 'Learning_rate': lr}
+        for k in train_err:
+            row[f'Train_{k}'], row[f'Valid_{k}'], row[f'Memory_{k}'] = \
+                train_err[k], valid_err[k], memory_err[k]
+        val = next((valid_err[k] for k in valid_err if best_metric in k), None)
+        if val is None:
+            raise KeyError(f'best_metric {best_metric!r} matches no recorded metric: '
+                           f'{", ".join(valid_err)}')
+        trainer.scheduler_step(val)
+        yield row

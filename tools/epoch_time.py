@@ -12,13 +12,20 @@ an MD-snapshot dataset; at 0.05 every structure has 1512 edges and a shuffled
 batch never meets a new shape.  Model and configuration are ``bench_train``'s
 (rehearsal + EWC, Adam, ``hip_graph`` on).
 
-Two arms in one process, same structures, same orders (epoch k of a loader with
+Three arms in one process, same structures, same orders (epoch k of a loader with
 seed s is ``default_rng(s + k).permutation``):
 
   parent  host ``train.labeled_graph`` once, then ``train.collate(..., device)``
           per batch and ``Trainer.rehearsal_step``; validation batches likewise
   loader  ``DeviceDataset.from_structures`` once, then ``DeviceLoader``s through
           ``Trainer.run_one_epoch_rehearsal`` / ``run_one_epoch``
+
+  records the loader arm with three ``ErrorRecorder``s (train, memory inside the
+          captured step; validation) and ``Trainer.validate`` on the served
+          kernels (``--no-records`` skips it).  Per epoch it also times, on its
+          own parameters and alternating: the eager validation pass with and
+          without a recorder, the served pass (refresh included) and the
+          ``set_weights`` host repack alone
 
 Per arm: the dataset preparation, a first epoch (it holds the captures), then
 ``--reps`` steady epochs alternating parent / loader, each timed with the host
@@ -31,7 +38,9 @@ conditions:
   * every steady loader epoch has eager == 0 and device_sorts == 0;
   * the loader arm captures at most 4 graphs over the whole run;
   * the two arms' parameter moves agree within 1e-2 in relative norm (the bar
-    of tests/test_gpu_loader.py (c)).
+    of tests/test_gpu_loader.py (c));
+  * with the records arm: the served validation pass, refresh included, is
+    faster than the eager one with a recorder in every alternating pair.
 
 An untimed control arm (``--no-control`` skips it) repeats the loader arm: a
 second trainer and second loaders, same seeds, same batches.  Every epoch
@@ -79,6 +88,8 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--no-control', dest='control', action='store_false',
                     help='skip the untimed control arm (the loader arm repeated)')
+    ap.add_argument('--no-records', dest='records', action='store_false',
+                    help='skip the records arm (recorders + served validation)')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'epoch_time.log'))
     a = ap.parse_args()
     import torch
@@ -103,7 +114,7 @@ def main():
                'scheduler_param': {'gamma': 0.99}, 'is_ddp': False, 'device': dev,
                'hip_graph': True, 'explicit_grad': True, 'blas': 'rocblas',
                'continue': {'fisher_information': fisher, 'opt_params': opt, 'ewc_lambda': 1e5}}
-        return model, train.Trainer(model, cfg)
+        return model, train.Trainer(model, cfg), cfg
 
     def timed(fn):
         torch.cuda.synchronize(dev)
@@ -112,11 +123,12 @@ def main():
         torch.cuda.synchronize(dev)
         return time.perf_counter() - t0, out
 
-    mp, tp = trainer()      # parent arm
-    ml, tl = trainer()      # loader arm
+    mp, tp, cfg = trainer()      # parent arm
+    ml, tl, _ = trainer()        # loader arm
+    mr, tr_r, _ = trainer() if a.records else (None, None, None)   # records arm
     # control: the loader arm again -- how far two runs of the SAME batches
     # drift apart over these many steps
-    mc, tc = trainer() if a.control else (None, None)
+    mc, tc, _ = trainer() if a.control else (None, None, None)
     theta0 = mp.flat.detach().double().cpu()
     assert torch.equal(mp.flat, ml.flat)
     syms = mp.chemical_symbols
@@ -142,7 +154,12 @@ def main():
         return {k: DeviceLoader(data[k], a.batch, shuffle=k != 'val', seed=SEEDS.get(k, 0))
                 for k in sets}
 
-    loaders, loaders_c = make_loaders(), make_loaders()
+    loaders, loaders_c, loaders_r = make_loaders(), make_loaders(), make_loaders()
+    # the reference's FT_w_reEWC error_record
+    rec_cfg = dict(cfg, error_record=[[t, m] for m in ('RMSE', 'MAE', 'Loss')
+                                      for t in ('Energy', 'Force', 'Stress')] + [['TotalLoss', 'None']])
+    from sevennet_finetuning_amd.error_recorder import ErrorRecorder
+    recs = {k: ErrorRecorder.from_config(rec_cfg) for k in ('train', 'valid', 'memory', 'probe')}
     emit({'loader_shapes': {k: [list(s) for s in v.shapes] for k, v in loaders.items()}})
 
     # ---- the two epochs
@@ -168,6 +185,30 @@ def main():
         val = tr.run_one_epoch(lds['val'], is_train=False)
         return out, val
 
+    def records_epoch():
+        out = tr_r.run_one_epoch_rehearsal(loaders_r['new'], loaders_r['mem'], is_train=True,
+                                           error_recorder=recs['train'], mem_recorder=recs['memory'])
+        t_val, _ = timed(lambda: tr_r.validate(loaders_r['val'], recs['valid']))
+        return out, (t_val, {k: recs[k].epoch_forward() for k in ('train', 'valid', 'memory')})
+
+    def validation_probe():
+        """the validation pass alone on the records arm's parameters, alternating"""
+        def eager_rec():
+            tr_r.run_one_epoch(loaders_r['val'], False, recs['probe'])
+            return recs['probe'].epoch_forward()
+
+        def served():
+            tr_r.validate(loaders_r['val'], recs['probe'])
+            return recs['probe'].epoch_forward()
+        t_plain, _ = timed(lambda: tr_r.run_one_epoch(loaders_r['val'], False))
+        t_eager, m_eager = timed(eager_rec)
+        t_served, m_served = timed(served)
+        t_set, _ = timed(lambda: tr_r._served.set_weights(mr.flat))
+        return {'eager_no_recorder_s': t_plain, 'eager_with_recorder_s': t_eager,
+                'served_with_recorder_refresh_included_s': t_served, 'set_weights_s': t_set,
+                'max_metric_abs_diff_served_vs_eager':
+                    max(abs(m_served[k] - m_eager[k]) for k in m_eager)}
+
     def counted(tr, fn):
         before = dict(tr._graphed.stats)
         dt, (out, val) = timed(fn)
@@ -179,7 +220,8 @@ def main():
         r = ref.flat.detach().double().cpu() - theta0
         return float((d - r).norm() / r.norm())
 
-    secs = {'parent': [], 'loader': []}
+    secs = {'parent': [], 'loader': [], 'records': []}
+    probes, records_val = [], []
     steady_stats, losses = [], {'parent': [], 'loader': []}
     for rep in range(a.reps + 1):
         for arm, tr, fn in (('parent', tp, parent_epoch), ('loader', tl, loader_epoch)):
@@ -197,6 +239,20 @@ def main():
                 secs[arm].append(dt)
             losses[arm] += [(float(x), float(y)) for x, y in out]
             emit(rec)
+        if a.records:
+            dt, st, out, (t_val, rows) = counted(tr_r, records_epoch)
+            probe = validation_probe()
+            emit({'arm': 'records', 'epoch': rep, 'first': rep == 0, 'seconds': round(dt, 4),
+                  'validate_s': round(t_val, 4), 'steps': len(out), 'stats': st,
+                  'valid': rows['valid'], 'train_TotalLoss': rows['train']['TotalLoss'],
+                  'memory_TotalLoss': rows['memory']['TotalLoss'],
+                  'validation_probe': {k: round(v, 6) if k.endswith('_s') else v
+                                       for k, v in probe.items()},
+                  'param_move_rel_diff_to_loader': move_diff(mr, ml)})
+            if rep:
+                secs['records'].append(dt)
+                records_val.append(t_val)
+                probes.append(probe)
         if a.control:
             loader_epoch(tc, loaders_c)
             emit({'arm': 'control (the loader arm repeated; untimed)', 'epoch': rep,
@@ -219,6 +275,25 @@ def main():
                                                          parent_batches('mem', keep))])[0]
                for _ in range(a.reps))
     steps = len(loaders['new'])
+    records = None
+    if a.records and probes:
+        eager = [p['eager_with_recorder_s'] for p in probes]
+        plain = [p['eager_no_recorder_s'] for p in probes]
+        served = [p['served_with_recorder_refresh_included_s'] for p in probes]
+        # the training steps' share of each arm's epoch: the epoch less its validation pass
+        train_rec = [e - v for e, v in zip(secs['records'], records_val)]
+        train_plain = [e - v for e, v in zip(secs['loader'], plain)]
+        records = {'epoch_s': [round(s, 3) for s in secs['records']],
+                   'validate_in_epoch_s': [round(s, 4) for s in records_val],
+                   'validation_eager_with_recorder_s': [round(s, 4) for s in eager],
+                   'validation_eager_no_recorder_s': [round(s, 4) for s in plain],
+                   'validation_served_refresh_included_s': [round(s, 4) for s in served],
+                   'set_weights_s': [round(p['set_weights_s'], 4) for p in probes],
+                   'set_weights_share_of_served_pass': round(
+                       min(p['set_weights_s'] for p in probes) / min(served), 3),
+                   'recorders_ms_per_training_step_as_measured':
+                       [round(1e3 * (x - y) / steps, 3) for x, y in zip(train_rec, train_plain)],
+                   'served_faster_in_every_pair': all(x < y for x, y in zip(served, eager))}
     emit({'summary': 'epoch_time', 'steps_per_epoch': steps,
           'parent_epoch_s': [round(s, 3) for s in secs['parent']],
           'loader_epoch_s': [round(s, 3) for s in secs['loader']],
@@ -231,7 +306,10 @@ def main():
                              'loader': tl._graphed.stats['captured']},
           'param_move_rel_diff': move, 'max_step_loss_rel_diff': loss_rel,
           'loader_vs_its_repeat_param_move_rel_diff': move_diff(ml, mc) if a.control else None,
-          'pass': {'steady_loader_epochs_all_replayed':
+          'records': records,
+          'pass': {**({'served_validation_faster_in_every_pair': records['served_faster_in_every_pair']}
+                      if records else {}),
+                   'steady_loader_epochs_all_replayed':
                    all(s['eager'] == 0 and s['device_sorts'] == 0 for s in steady_stats),
                    'loader_captured_at_most_4': tl._graphed.stats['captured'] <= 4,
                    'param_moves_agree_1e-2': move < 1e-2}})
