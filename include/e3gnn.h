@@ -143,7 +143,12 @@ typedef struct e3gnn_gemm_desc {
    * (tm, tn) reads entry tm * krange_stride_m + tn) four int32 -- the k
    * ranges [lo1, hi1) of the first operand pair and [lo2, hi2) of the second
    * that can be nonzero; the product skips the rest (a linear's dense matrix
-   * is block-diagonal by l).  krange_stride_m = 0: one entry per column tile. */
+   * is block-diagonal by l).  krange_stride_m = 0: one entry per column tile.
+   * The kernel rounds a range outward to whole k steps and clamps it to its
+   * own pair: hi >= K means "to the end of that pair" (1 << 30: the whole K),
+   * lo >= hi an empty range (beta 0 still writes the tile's zeros).  In k
+   * rows of a one-segment operand: krange with a layout of more than one K
+   * segment (ks < K) in either pair is refused with E3GNN_ERR_ARG. */
   const int32_t* krange;
   int32_t krange_stride_m;
   /* nullable: the general layouts (then lda.. / trans_* / ldc are unused) */

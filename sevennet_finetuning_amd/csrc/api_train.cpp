@@ -87,6 +87,16 @@ static int gemm_prob(const e3gnn_gemm_desc& q, int i, TgProb& p) {
       return fail(E3GNN_ERR_ARG, "e3gnn_gemm_grouped: problem " + std::to_string(i) +
                                      " addresses an operand beyond 2 GB (32-bit buffer offsets)");
   }
+  // krange counts k rows; the kernel turns it into k steps, and with every
+  // segment padded to whole steps a step index is k / BK in a one-segment
+  // pair only
+  if (q.krange && q.layout) {
+    const e3gnn_gemm_layouts& L = *q.layout;
+    auto segs = [](int K, int ks) { return K > 0 && ks > 0 && ks < K; };
+    if (segs(q.k, L.a.ks) || segs(q.k, L.b.ks) || segs(q.k2, L.a2.ks) || segs(q.k2, L.b2.ks))
+      return fail(E3GNN_ERR_ARG, "e3gnn_gemm_grouped: problem " + std::to_string(i) +
+                                     " has krange with a layout of several K segments");
+  }
   p.C = q.c;
   p.M = q.m; p.N = q.n; p.K1 = q.k; p.K2 = q.k2;
   p.alpha = q.alpha; p.beta = q.beta;

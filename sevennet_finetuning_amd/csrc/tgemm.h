@@ -31,7 +31,8 @@ struct TgProb {
   float alpha;
   int beta;
   int splits;  // requested (tg_add settles it)
-  const int* kr;  // per-tile k ranges [lo1, hi1, lo2, hi2) (nullable; e3gnn_gemm_desc::krange)
+  const int* kr;  // per-tile k ranges [lo1, hi1, lo2, hi2) (nullable; e3gnn_gemm_desc::krange),
+                  // clamped to each pair's own steps; one-segment pairs only (gemm_prob)
   int kr_sm;      // its row-tile stride (0: per column tile)
   // set by tg_add
   int mode;   // tile shape: 0 = 64 x 64 x 16, 1 = 32 x 32 x 32 with the waves over k

@@ -147,6 +147,11 @@ __device__ __forceinline__ void tg_tile(const TgProb& P, int local, float* lds) 
     n1 = max(0, rfl((q[1] + BK - 1) / BK) - kb1);
     kb2 = rfl(q[2] / BK);
     n2 = max(0, rfl((q[3] + BK - 1) / BK) - kb2);
+    // a range never leaves its own pair: hi beyond K means "to the pair's
+    // end" (step kb1 + n1 would otherwise be taken from a segment past the
+    // first pair's last, and the second pair never started)
+    n1 = min(n1, max(0, nk1 - kb1));
+    n2 = min(n2, max(0, nk - nk1 - kb2));
   }
   const int jb = rfl(s * P.ksteps), je = min(n1 + n2, jb + rfl(P.ksteps));
   auto kt_of = [&](int j) { return j < n1 ? kb1 + j : nk1 + kb2 + (j - n1); };
